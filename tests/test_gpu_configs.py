@@ -343,7 +343,7 @@ def _bench(args, env=None):
 
 
 def test_bench_two_ranks_as_a_bare_command():
-    """`python bench.py --gpus 2` with no launcher around it: bench.py re-executes itself through
+    """`python bench.py --gpus 2` with no launcher around it: bench.py runs itself as a child through
     torch.distributed.run, the two ranks shard the corpus (2 + 2 buffers), gather the results, rank 0 prints one line
     with n_gpus = 2 -- and the gathered dictionaries / activations are those of one rank running all 4 buffers.  On a
     box with fewer GPUs than ranks the ranks share the device and the gather goes through gloo; with >= 2 GPUs this is
@@ -367,7 +367,7 @@ def test_bench_eight_ranks_rehearsed_on_one_gpu():
     running the same 32 buffers: same order-sensitive checksum, rank r holds shard_range(32, 8, r)."""
     sys.path.insert(0, os.path.join(ROOT, "flucoma-core_amd"))
     import sharding
-    common = ["--steps", "1", "--warmup", "1", "--iters", "3", "--no-cpu-baseline"]
+    common = ["--full", "--steps", "1", "--warmup", "1", "--iters", "3", "--no-cpu-baseline"]
     eight = _bench(["--gpus", "8", "--buffers", "4", *common], env={"FLUHIP_BENCH_BACKEND": "gloo"})
     one = _bench(["--gpus", "1", "--buffers", "32", *common])
     assert eight["n_gpus"] == 8 and eight["total_buffers"] == one["total_buffers"] == 8 * 4
@@ -383,7 +383,7 @@ def test_bench_one_rank_rccl_group_executes_the_collectives():
     process group and runs the N > 1 job's collective code as written -- all_gather_into_tensor of the device-resident
     dictionaries / activations inside every step, the MAX all-reduce of the step time on a device tensor, the barriers --
     with no `world > 1` short cut.  Same floats as the plain single-process run."""
-    common = ["--gpus", "1", "--buffers", "4", "--steps", "2", "--warmup", "1", "--iters", "3", "--no-cpu-baseline"]
+    common = ["--gpus", "1", "--buffers", "4", "--steps", "2", "--warmup", "1", "--iters", "3", "--full", "--no-cpu-baseline"]
     grp = _bench(common, env={"FLUHIP_BENCH_BACKEND": "nccl"})
     one = _bench(common)
     assert grp["backend"].startswith("rccl") and "one-rank group" in grp["backend"] and one["backend"] == "single process"
@@ -393,6 +393,31 @@ def test_bench_one_rank_rccl_group_executes_the_collectives():
     r = grp["roofline"]
     assert r["shader_cycles_per_launch"] > 0 and 500 < r["sustained_mhz"] < 2600
     assert r["clock_stamps"]["w"]["launches"] == r["clock_stamps"]["h"]["launches"] == 3 * 3   # 2 timed + 1 profiled step
+
+
+def test_bench_dump_outputs_are_the_last_steps_floats(tmp_path):
+    """--dump-outputs DIR: the bases / activations of the last timed step, every buffer in global buffer order, float32 --
+    the floats the line's checksum weighs; the same with --full (what moved behind it runs after the timed steps and
+    changes nothing they compute).  A plain run carries the headline without the figures --full adds."""
+    common = ["--gpus", "1", "--buffers", "4", "--steps", "2", "--warmup", "1", "--iters", "3"]
+    plain = _bench([*common, "--dump-outputs", str(tmp_path / "plain")])
+    full = _bench([*common, "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])
+    b = np.load(tmp_path / "plain" / "bases.npy")
+    a = np.load(tmp_path / "plain" / "activations.npy")
+    assert b.dtype == a.dtype == np.float32 and b.shape == (4, 32, 1025) and a.shape == (4, 32, 862)
+    assert sorted(os.listdir(tmp_path / "plain")) == ["activations.npy", "bases.npy"]
+    w = np.arange(1, 5, dtype=np.float64)
+    dumped = float((w * (b.astype(np.float64).sum(axis=(1, 2)) + a.astype(np.float64).sum(axis=(1, 2)))).sum())
+    assert dumped == pytest.approx(plain["result_checksum"], rel=1e-12)
+    assert np.array_equal(np.load(tmp_path / "full" / "bases.npy"), b)
+    assert np.array_equal(np.load(tmp_path / "full" / "activations.npy"), a)
+    assert plain["result_checksum"] == full["result_checksum"] and plain["steps"] == full["steps"] == 2
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in plain and key in full
+    assert plain["ms_per_step"] > 0 and plain["value"] == pytest.approx(4 * 3 * 1e3 / plain["ms_per_step"])
+    for key in ("roofline", "roofline_stft", "job_wall_ms_host_buffers_in_and_out", "cpu_baseline"):
+        assert key not in plain
+    assert "roofline" in full and "job_wall_ms_host_buffers_in_and_out" in full
 
 
 def _rccl_worker(q, root):

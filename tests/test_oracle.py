@@ -211,18 +211,13 @@ def test_resynth_oracles_agree(oracle, onp):
 
 
 def test_reference_wav_c1_when_available(oracle, onp):
-    """Plumbing config c1 on the real bundled WAV; only where /root/reference exists (never on
-    the GPU box)."""
-    path = "/root/reference/Resources/AudioFiles/Nicol-LoopE-M.wav"
-    if not os.path.exists(path):
-        pytest.skip("reference resources not present")
-    import wave
-    with wave.open(path, "rb") as w:
-        assert w.getnchannels() == 1 and w.getsampwidth() == 2 and w.getframerate() == 44100
-        n = w.getnframes()
-        pcm = np.frombuffer(w.readframes(n), dtype="<i2")
+    """Plumbing config c1 on the bundled WAV's samples (Nicol-LoopE-M.wav, 16-bit mono 44.1 kHz: all of them travel in
+    tests/golden/reference_c1.npz, tools/make_reference_c1_fixture.py): both oracles on the whole spectrogram and factors."""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_c1.npz"))
+    assert float(g["sample_rate"]) == 44100 and g["pcm16"].dtype == np.int16 and g["pcm16"].ndim == 1
+    n = len(g["pcm16"])
     assert n == 453932
-    x = (pcm.astype(np.float32) / 32768.0)
+    x = (g["pcm16"].astype(np.float32) / 32768.0)
     bases, acts, mag = oracle.bufnmf_channel(x, 1024, 1024, 512, 3, 50, 42, want_mag=True)
     b2, a2, m2, *_ = onp.bufnmf_channel(x, 1024, 1024, 512, 3, 50, 42)
     assert mag.shape == (887, 513)
@@ -405,21 +400,6 @@ def test_feature_framing_follows_from_fluidsource(oracle, onp, n, win, hop, padd
 
 
 # ---- a pin on the REAL reference's outputs: its pre-analysed demo corpus -----------------------------------------------
-def _wav_mono(path):
-    import wave
-    w = wave.open(path, "rb")
-    ch, sw, nf = w.getnchannels(), w.getsampwidth(), w.getnframes()
-    raw = w.readframes(nf)
-    w.close()
-    if sw == 2:
-        x = np.frombuffer(raw, "<i2").astype(np.float64) / 32768.0
-    else:
-        assert sw == 3
-        b = np.frombuffer(raw, np.uint8).reshape(-1, 3)
-        x = (b[:, 0].astype(np.int32) | (b[:, 1].astype(np.int32) << 8) | (b[:, 2].astype(np.int8).astype(np.int32) << 16)) / 8388608.0
-    return x.reshape(-1, ch)[:, 0].astype(np.float32)
-
-
 def _mfcc_stats(m):
     """BufStats' mean and standard deviation per coefficient (algorithms/util/WeightedStats.hpp:34-35: uniform weights
     1 / N, i.e. the population form), flattened as the corpus rows are: 13 means, then 13 deviations"""
@@ -431,43 +411,30 @@ def test_oracles_reproduce_the_references_pre_analysed_corpus(oracle, onp):
     """flucoma-core ships the output of a FluCoMa build: Resources/Data/flucoma_corpus_mfcc.json holds, for 1086 slices of
     its concatenated demo files, the mean and deviation over the slice's frames of BufMFCC's coefficients 1..13 (info.txt:
     "pre-analysed MFCCs of the FluCoMa demo audio files in small slices"; slice points in flucoma_corpus_slices.wav, file
-    order in flucoma_corpus_files.json).  The first three files are present here, so the 299 slices inside them can be
-    recomputed: both oracles -- sample read, Hann window, the buffered clients' framing and padding, the unnormalised FFT,
+    order in flucoma_corpus_files.json).  299 slices lie inside the first three files; 27 of them travel with their rows in
+    tests/golden/reference_corpus_mfcc_sample.npz (tools/make_reference_corpus_sample_fixture.py: slice 0, the two that
+    straddle a file boundary, 8 short ones per file, seeded) and are recomputed: both oracles -- sample read, Hann window, the buffered clients' framing and padding, the unnormalised FFT,
     magnitude, 40 mel bands, 20 log10, DCT-II, startCoeff -- land on the reference's numbers to the float32 the JSON
     stores (3.6e-6 on values up to 60), on 16-bit 44.1 kHz and 24-bit 48 kHz material.  None / Full padding or startCoeff 0
     miss by 0.3 .. 240.  This is the one place where the restatements meet outputs of the reference itself; the STFT half of
     it (a1 - a5 of SURVEY 8) is the BufNMF path's own."""
-    import json
-    import struct
-    R = "/root/reference/Resources/"
-    if not os.path.exists(R + "Data/flucoma_corpus_mfcc.json"):
-        pytest.skip("reference checkout not present")
-    names = json.load(open(R + "Data/flucoma_corpus_files.json"))["data"]
-    first3 = [names[str(i)][0] for i in range(3)]
-    if not all(os.path.exists(R + "AudioFiles/" + f) for f in first3):
-        pytest.skip("demo audio files not present")
-    cat = np.concatenate([_wav_mono(R + "AudioFiles/" + f) for f in first3])
-    raw = open(R + "Data/flucoma_corpus_slices.wav", "rb").read()
-    i = raw.find(b"data")
-    points = np.frombuffer(raw[i + 8:i + 8 + struct.unpack("<I", raw[i + 4:i + 8])[0]], "<f4").astype(np.int64)
-    rows = json.load(open(R + "Data/flucoma_corpus_mfcc.json"))["data"]
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_corpus_mfcc_sample.npz"))
+    slices, off = g["slices"], g["offsets"]
+    seg = lambda j: (g["pcm24"][off[j]:off[j + 1]].astype(np.float64) / 8388608.0).astype(np.float32)
+    assert set(g["source_file"].tolist()) == {0, 1, 2} and slices[0] == 0
     checked, worst = 0, 0.0
-    for k in range(len(points) - 1):
-        a, b = int(points[k]), int(points[k + 1])
-        if b > len(cat):
-            break
-        ref = np.array(rows["%d.000000" % k])
-        got_np = _mfcc_stats(onp.bufmfcc_channel(cat[a:b], 1024, 1024, 512, 40, 13, 1))
-        got_c = _mfcc_stats(oracle.bufmfcc_channel(cat[a:b], 1024, 1024, 512, 40, 13, 1))
+    for j in range(len(slices)):
+        ref = g["expected"][j]
+        got_np = _mfcc_stats(onp.bufmfcc_channel(seg(j), 1024, 1024, 512, 40, 13, 1))
+        got_c = _mfcc_stats(oracle.bufmfcc_channel(seg(j), 1024, 1024, 512, 40, 13, 1))
         worst = max(worst, np.abs(got_np - ref).max(), np.abs(got_c - ref).max())
         checked += 1
-    assert checked == 299, checked
+    assert checked == len(slices) == 27, checked
     assert worst < 2e-5, worst
     # and the parameters are not a coincidence: slice 0 with the neighbouring choices
-    ref0 = np.array(rows["0.000000"])
-    a, b = int(points[0]), int(points[1])
-    assert np.abs(_mfcc_stats(onp.bufmfcc_channel(cat[a:b], 1024, 1024, 512, 40, 13, 0)) - ref0).max() > 100      # startCoeff 0
-    assert np.abs(_mfcc_stats(onp.bufmfcc_channel(cat[a:b], 1024, 1024, 512, 40, 13, 1, padding_mode=0)) - ref0).max() > 0.1
+    ref0 = g["expected"][0]
+    assert np.abs(_mfcc_stats(onp.bufmfcc_channel(seg(0), 1024, 1024, 512, 40, 13, 0)) - ref0).max() > 100      # startCoeff 0
+    assert np.abs(_mfcc_stats(onp.bufmfcc_channel(seg(0), 1024, 1024, 512, 40, 13, 1, padding_mode=0)) - ref0).max() > 0.1
 
 
 def test_reference_corpus_fixture_is_what_the_oracles_give(oracle, onp):

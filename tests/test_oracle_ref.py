@@ -5,18 +5,18 @@ HISSTools and stay "parity unpinned" (DESIGN section 5)."""
 import os
 import subprocess
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref", "refcheck")
+# what oracle/_ref/refcheck prints, recorded: the comparison needs no reference sources at hand
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_refcheck.txt")
 
 
 def _ref_lines():
-    if os.path.isdir("/root/reference/include/flucoma"):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "oracle")], check=True, capture_output=True)
-    if not os.path.exists(REF):
-        pytest.skip("oracle/_ref/refcheck is not built and /root/reference is not here to build it from")
-    return subprocess.run([REF], check=True, capture_output=True, text=True).stdout.splitlines()
+    with open(GOLDEN) as f:
+        want = f.read().splitlines()
+    if os.path.exists(REF):     # built by build() where the reference headers are present: the recording must still hold
+        assert subprocess.run([REF], check=True, capture_output=True, text=True).stdout.splitlines() == want
+    return want
 
 
 def _mirror_lines(tmp_path):

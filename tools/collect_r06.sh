@@ -3,9 +3,9 @@
 # the PMC passes of the update kernel (tied to the kernel source by its hash), the perf matrix, the rocprofv3 kernel stats of the
 # ragged 64 x 40 corpus, and the per-config sets for c2, c3, c5
 export TMPDIR=/tmp; tag=${1:-final}; out=${2:-gpurun_out/r06final}; mkdir -p $out
-python bench.py > $out/bench_$tag.json 2> $out/bench_$tag.err
+python bench.py --full > $out/bench_$tag.json 2> $out/bench_$tag.err
 d=$out/ks; rm -rf $d
-rocprofv3 --kernel-trace --stats --output-format csv -d $d -o b -- python bench.py --no-cpu-baseline --configs none > $out/ks.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $d -o b -- python bench.py --full --no-cpu-baseline --configs none > $out/ks.log 2>&1
 find $d -name '*kernel_stats.csv' -exec cp {} $out/bench_${tag}_kernel_stats.csv \;
 rm -rf $d
 rm -rf $out/pmc; bash tools/pmc_bench.sh $out/pmc --configs none > $out/pmc_passes.txt 2>&1

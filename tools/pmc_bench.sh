@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 mkdir -p $out
 run() { # name, counters...
   name=$1; shift
-  timeout 300 rocprofv3 --pmc "$@" --output-format csv -d $out -o $name -- python bench.py --steps 1 --warmup 0 --iters 6 --no-cpu-baseline "${EXTRA[@]}" > $out/$name.log 2>&1
+  timeout 300 rocprofv3 --pmc "$@" --output-format csv -d $out -o $name -- python bench.py --full --steps 1 --warmup 0 --iters 6 --no-cpu-baseline "${EXTRA[@]}" > $out/$name.log 2>&1
 }
 EXTRA=("$@")
 run sq SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE

@@ -3,7 +3,7 @@
 # (A/B build: FLUHIP_SIDE_STREAM=0 one stream as before, =1 forked / joined); same box, alternating
 export TMPDIR=/tmp; out=gpurun_out/r04p8; mkdir -p $out
 for v in 0 1 0 1 0 1; do
-  env FLUHIP_AB=1 FLUHIP_SIDE_STREAM=$v python bench.py --no-cpu-baseline --configs none 2>/dev/null | python -c "
+  env FLUHIP_AB=1 FLUHIP_SIDE_STREAM=$v python bench.py --full --no-cpu-baseline --configs none 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('side_stream=$v', round(d['value']), 'buffer-iterations/s', round(d['ms_per_step'],2), 'ms/step; update launch', round(r['avg_launch_ms']*1e3,1), 'us; checksum', d.get('result_checksum'), d.get('schedule'))" | tee -a $out/side_stream.txt

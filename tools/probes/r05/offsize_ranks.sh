@@ -8,7 +8,7 @@ RANKS=${*:-"20 32 40 48 56 64 80 96 100 128"}
 for rep in 1 2; do
   for K in $RANKS; do
     for off in 1 0; do
-      r=$(FLUHIP_OFFSIZE=$off python bench.py --rank $K --iters 50 --steps 3 --warmup 1 --no-cpu-baseline --configs none 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.readline()); print(round(j['ms_per_step'],2), round(j['roofline']['avg_launch_ms']*1e3,1))")
+      r=$(FLUHIP_OFFSIZE=$off python bench.py --full --rank $K --iters 50 --steps 3 --warmup 1 --no-cpu-baseline --configs none 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.readline()); print(round(j['ms_per_step'],2), round(j['roofline']['avg_launch_ms']*1e3,1))")
       echo "rank $K offsize=$off: ms per step (50 it), us per update launch: $r"
     done
   done
