@@ -35,7 +35,7 @@ VARIANTS = {
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
-SOURCES = ["kernels_stft.hip", "kernels_stft2.hip", "kernels_nmf.hip", "kernels_nmf5.hip", "kernels_nmf5_off.hip", "kernels_nmf_strip.hip", "kernels_nmf_bintile.hip", "kernels_nmf_wide.hip", "kernels_istft.hip", "kernels_feat.hip", "kernels_svd.hip", "api_core.hip", "api_corpus.hip", "api_algorithms.hip", "api_features.hip", "api_frames.hip", "api_pool.cpp"]
+SOURCES = ["kernels_stft.hip", "kernels_stft2.hip", "kernels_nmf.hip", "kernels_nmf5.hip", "kernels_nmf5_off.hip", "kernels_nmf_strip.hip", "kernels_nmf_bintile.hip", "kernels_nmf_wide.hip", "kernels_istft.hip", "kernels_feat.hip", "kernels_svd.hip", "kernels_range.hip", "api_core.hip", "api_corpus.hip", "api_algorithms.hip", "api_features.hip", "api_frames.hip", "api_pool.cpp"]
 # kernel forms no production shape reaches are not part of the production library (kernels_nmf_bintile.hip was 415
 # lines of dead weight in lib/libflucoma_hip.so): compiled into the measurement builds only
 AB_ONLY = {"kernels_nmf_bintile.hip"}

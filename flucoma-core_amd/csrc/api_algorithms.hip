@@ -5,6 +5,7 @@
 //   algorithm::NNDSVD / BufNMFSeed         NNDSVD.hpp:30-132, clients/nrt/NMFSeedClient.hpp:73-131   fluhip_nndsvd_f64, fluhip_bufnmfseed_f32
 //   the channel-loop body of BufNMF        clients/nrt/NMFClient.hpp:240-334                         fluhip_bufnmf_channel_f32
 #include "api_internal.h"
+#include "range_scale.h"
 
 extern "C" {
 
@@ -21,7 +22,10 @@ static int stft_common(fluhip_ctx* ctx, const float* a32, const double* a64, int
   fluhip_corpus c;
   c.ctx = ctx; c.B = 1; c.n = n; c.win = win; c.fft = fft; c.hop = hop; c.K = 1;
   c.windowType = window_type;
-  c.keepSpec = spec != nullptr;
+  // the magnitudes come from the spectrum by hypot (launch_mag_hypot below): std::abs of std::complex (alg/STFT.hpp:61-66)
+  // over the whole double range and an exact 0 for silence, where the STFT kernels' own sqrt(re^2 + im^2) from DBL_MIN --
+  // the float corpus path's form -- gives 1.5e-154 for a silent bin and leaves the range beyond 1e+-154
+  c.keepSpec = spec != nullptr || mag != nullptr;
   c.stftOnly = true;   // STFT::process + magnitude: the frame-major magnitudes (and the spectrum), nothing for factor updates
   rc = corpus_alloc(ctx, &c);
   if (rc) return rc;
@@ -33,6 +37,8 @@ static int stft_common(fluhip_ctx* ctx, const float* a32, const double* a64, int
                              ctx->stream));
   rc = corpus_stft(&c, a32 ? in.as<float>() : nullptr, a32 ? nullptr : in.as<double>(), n, true);
   if (rc) return rc;
+  if (mag) launch_mag_hypot(c.spec.as<double>(), (int) c.T, (int) c.F, c.mag.as<double>(), c.Fp, ctx->stream);
+  HIPCHK(ctx, hipGetLastError());
   if (frames_out) *frames_out = c.T;
   // (long buffers: through the pinned staging blocks -- a minute of audio at fft 2048 is 42 + 85 MB)
   if (mag && (rc = copy_to_host(ctx, mag, (size_t) c.F * sizeof(double), c.mag.p, (size_t) c.Fp * sizeof(double),
@@ -142,6 +148,15 @@ int fluhip_nmf_process_views_f64(fluhip_ctx* ctx, const fluhip_matrix_view* Xv, 
                                  (size_t) F * sizeof(double), (size_t) T, hipMemcpyHostToDevice, s));
     launch_transpose(c.mag.as<double>(), c.Fp, c.Tp * c.Fp, c.magT.as<double>(), c.Tp, c.Fp * c.Tp, (int) T, (int) F, 1, s);
   }
+  // double-precision input of any magnitude: above 2^128 the reciprocal trees of the factor updates (recip_tree.h) would
+  // overflow, so X goes in scaled by 2^-e (range_scale.h, decided on the device; nothing is written for max|X| <= 2^128)
+  // and H1 -- which scales with X through the updates while W does not -- comes back times 2^e.  Seeds need nothing:
+  // alg/NMF.hpp:152-153 normalises them.
+  DevBuf xmax;
+  HIPCHK(ctx, xmax.alloc(sizeof(double), true, s));
+  launch_absmax(c.mag.as<double>(), c.Fp, (int) T, (int) F, xmax.as<double>(), s);
+  launch_nmf_range_scale(c.mag.as<double>(), c.Fp, (int) T, (int) F, xmax.as<double>(), -1, s);
+  launch_nmf_range_scale(c.magT.as<double>(), c.Tp, (int) F, (int) T, xmax.as<double>(), -1, s);
   c.haveMag = true;
   // seeds are small (K x F, T x K): contiguous host images whatever their strides
   std::vector<double> w0tmp, h0tmp;
@@ -162,6 +177,8 @@ int fluhip_nmf_process_views_f64(fluhip_ctx* ctx, const fluhip_matrix_view* Xv, 
   rc = corpus_iterate(&c, iters, update_w != 0, update_h != 0, progress, user);
   if (rc != FLUHIP_OK && rc != FLUHIP_CANCELLED) return rc;
   const bool cancelled = rc == FLUHIP_CANCELLED;
+  // H (and with it V1 = W H) is X's scale only once it has been updated; W-only runs keep the normalised seed
+  if (update_h && iters > 0) launch_nmf_range_scale(c.H1.as<double>(), c.Kp, (int) T, (int) c.Kp, xmax.as<double>(), 1, s);
   // alg/NMF.hpp:127-133 outputs; :182 V = W*H only when the loop ran to completion
   DevBuf dw, dh, dv, dvt;
   std::vector<double> w1tmp, h1tmp, v1tmp;
@@ -290,8 +307,14 @@ int fluhip_nmf_process_frames_f64(fluhip_ctx* ctx, const double* X, int64_t T, i
   HIPCHK(ctx, c.mag.alloc((size_t) c.Tp * c.Fp * sizeof(double), true, s));
   HIPCHK(ctx, hipMemcpy2DAsync(c.mag.p, (size_t) c.Fp * sizeof(double), X, (size_t) ldx * sizeof(double),
                                (size_t) F * sizeof(double), (size_t) T, hipMemcpyHostToDevice, s));
+  // the range rescaling of fluhip_nmf_process_views_f64: H (a linear function of X once updated) comes back times 2^e
+  DevBuf xmax;
+  HIPCHK(ctx, xmax.alloc(sizeof(double), true, s));
+  launch_absmax(c.mag.as<double>(), c.Fp, (int) T, (int) F, xmax.as<double>(), s);
+  launch_nmf_range_scale(c.mag.as<double>(), c.Fp, (int) T, (int) F, xmax.as<double>(), -1, s);
   int rc = process_frames_on_device(ctx, c, W0, iters, seed);
   if (rc != FLUHIP_OK) return rc;
+  if (iters > 0) launch_nmf_range_scale(c.H1.as<double>(), c.Kp, (int) T, (int) c.Kp, xmax.as<double>(), 1, s);
   DevBuf dh, dv;
   if (H)
   {
@@ -326,6 +349,16 @@ static int nndsvd_device(fluhip_ctx* ctx, double* G, int64_t F, int64_t T, int64
   HIPCHK(ctx, dJ.alloc((size_t) F * F * sizeof(double), false, st));
   HIPCHK(ctx, dN.alloc((size_t) F * sizeof(double), false, st));
   HIPCHK(ctx, dFlag.alloc(sizeof(unsigned), true, st));
+  // the sweeps form sums of squares unscaled: G goes in times 2^-e with max|G| 2^-e in [0.5, 1) (range_scale.h; Eigen's
+  // BDCSVD and LAPACK scale first as well), the singular values come back times 2^e, U and V^T are unchanged
+  DevBuf dMax;
+  HIPCHK(ctx, dMax.alloc(sizeof(double), true, st));
+  launch_absmax(G, ldg, (int) F, (int) T, dMax.as<double>(), st);
+  double gmax = 0;
+  HIPCHK(ctx, hipMemcpyAsync(&gmax, dMax.p, sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  const int e = svd_range_exponent(gmax);
+  launch_scale_pow2(G, ldg, (int) F, (int) T, -e, st);
   const int sweeps = launch_jacobi_svd(G, ldg, (int) F, (int) T, dJ.as<double>(), dN.as<double>(), dFlag.as<unsigned>(),
                                        40, st);
   HIPCHK(ctx, hipGetLastError());
@@ -368,6 +401,7 @@ static int nndsvd_device(fluhip_ctx* ctx, double* G, int64_t F, int64_t T, int64
     if (sj > 0)
       for (int64_t t = 0; t < T; t++) VT[(size_t) j * T + t] /= sj;
   }
+  for (double& v : s) v = std::ldexp(v, e);
   return FLUHIP_OK;
 }
 

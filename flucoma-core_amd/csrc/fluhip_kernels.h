@@ -440,4 +440,14 @@ void launch_polar_to_spec(const float* mag, const float* phase, int T, int F, do
 int launch_jacobi_svd(double* G, int64_t ldg, int n, int T, double* Jt, double* norms, unsigned* flag, int maxSweeps,
                       hipStream_t s);
 
+// the range of the double-precision entry points (kernels_range.hip, range_scale.h)
+// *out (one zeroed double) = max(*out, max |p|) over rows x cols, row stride ld
+void launch_absmax(const double* p, int64_t ld, int rows, int cols, double* out, hipStream_t s);
+// p *= 2^(sign nmf_range_exponent(*maxAbs)), the exponent read on the device; no write when it is 0
+void launch_nmf_range_scale(double* p, int64_t ld, int rows, int cols, const double* maxAbs, int sign, hipStream_t s);
+// p *= 2^e
+void launch_scale_pow2(double* p, int64_t ld, int rows, int cols, int e, hipStream_t s);
+// mag[t][k] = hypot(re, im) of the interleaved spectrum [T][F]: exact over the whole double range, 0 for a silent bin
+void launch_mag_hypot(const double* spec, int T, int F, double* mag, int64_t ldMag, hipStream_t s);
+
 } // namespace fluhip

@@ -4,10 +4,12 @@
 // instruction on the FP64 datapath the MFMAs share, so a reciprocal costs four operation slots before its Newton step.  A
 // group shares one: a binary tree of products up (a[l][j] = the product of node j of level l), v_rcp_f64 + one Newton step
 // at the root (2^-46, as the single reciprocal of rounds 1 - 5), and the inverses handed down -- the inverse of a child is
-// the inverse of its parent times its sibling.  A group of n costs (n - 1) + 6 + 2 (n - 1) slots: 9 for two (rounds 2 - 5's
-// pairs), 12 for three, 15 for four, 21 for six, against 6 n alone.  Every product adds one rounding (1.1e-16) under the
-// Newton step's 1.4e-14.  Range: the root is a product of up to G operands in [eps, max Q]; with Q <= 3.4e38 * window
-// (any float input) a group of four reaches 2.4e167 and a group of six 1e251 -- inside the double range -- and eps^6 = 1e-94.
+// the inverse of its parent times its sibling.  A group of n costs (n - 1) + 6 + 2 (n - 1) slots: 9 for two (rounds 2 - 5),
+// 12 for three, 15 for four, 21 for six, against 6 n alone.  Every product adds one rounding (1.1e-16) under the
+// Newton step's 1.4e-14.  Range: the root is a product of up to G operands in [eps, max Q].  The factor updates see
+// max|X| <= 2^128 -- any float input, and double input above that is rescaled to it first (range_scale.h) -- so
+// Q <= 32769 bins * 2^128 and a group of six reaches 2^858 (four: 2^572), its reciprocal normal, and eps^6 = 1e-94
+// (tests/test_recip_tree.py checks every mix of operands at the two ends).
 // Written level by level across the groups: independent chains side by side for the in-order VALU.
 #pragma once
 

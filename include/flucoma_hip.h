@@ -104,7 +104,8 @@ int64_t fluhip_stft_num_frames(int64_t n, int64_t win, int64_t hop);
 /* Replaces STFT::STFT(win, fft, hop, windowType) + STFT::process(audio, spectrogram) +
  * STFT::magnitude(spectrogram, magnitude)  (algorithms/public/STFT.hpp:36-47, 90-108, 61-66).
  * audio: n host doubles with element stride `stride`.  spec (may be NULL): T*F interleaved
- * (re,im) doubles == std::complex<double>[T][F].  mag (may be NULL): T*F doubles. */
+ * (re,im) doubles == std::complex<double>[T][F].  mag (may be NULL): T*F doubles, |spec| by hypot -- exact over the whole
+ * double range, exactly 0 for a silent bin. */
 int fluhip_stft_f64(fluhip_ctx* ctx, const double* audio, int64_t n, int64_t stride, int64_t win,
                     int64_t fft, int64_t hop, int window_type, double* spec, double* mag,
                     int64_t* frames_out);
@@ -126,9 +127,12 @@ int fluhip_stft_f32(fluhip_ctx* ctx, const float* audio, int64_t n, int64_t stri
  * Numerics: FP64 throughout.  The quotients V / max(W H, eps) of the update loop are formed as V * (1 / d) with a Newton-
  * refined reciprocal, relative error <= 2^-46 (1.4e-14) per quotient instead of a correctly rounded division; measured,
  * the factors stay within 1e-13 of the restatement after 200 iterations (the tests assert 1e-9; north_star asks 1e-5).
- * Two quotients share one reciprocal 1 / (d d'): magnitudes whose products W H reach sqrt(DBL_MAX) ~ 1e154 overflow it
- * (the ratio becomes 0 there) -- far outside anything a spectrogram holds; build with -DFLUHIP_SHARED_RECIPROCAL=0
- * -DFLUHIP_QUOTIENT_CORRECTION=1 for division to the last bit over the whole double range. */
+ * The reciprocals of four quotients (six in the frame-strip kernel) come from one reciprocal of their product, which stays
+ * inside the double range while max|X| <= 2^128 (~3.4e38; any float input).  Larger X, up to DBL_MAX, is scaled by the
+ * smallest power of two 2^-e that brings it to 2^128 and H1 / V1 are scaled back by 2^e (exact; W is scale-free); input at
+ * or below 2^128 is not rescaled and keeps its arithmetic bit for bit.  The same holds for fluhip_nmf_process_frames_f64.
+ * One deviation: past ~1e154 the reference's own W.colwise().normalize() overflows and it returns zeros, where this
+ * library returns finite factors.  Build with -DFLUHIP_QUOTIENT_CORRECTION=1 for division to the last bit. */
 int fluhip_nmf_process_f64(fluhip_ctx* ctx, const double* X, int64_t T, int64_t F, int64_t ldx,
                            int64_t K, int64_t iters, int update_w, int update_h, int64_t seed,
                            const double* W0, const double* H0, double* W1, double* H1,
@@ -172,7 +176,8 @@ int fluhip_nmf_process_frames_f64(fluhip_ctx* ctx, const double* X, int64_t T, i
  * X: T x F with row stride ldx.  W: w_rows x F, H: T x w_rows (the reference's W.rows(); rows / columns >= k are
  * zero, or filled like the rest for methods 1 and 2, exactly as the reference treats its zero-initialised
  * outputs); k is returned in *rank_out and must not exceed w_rows.
- * The SVD is a one-sided Jacobi iteration on the device (kernels_svd.hip).  A singular pair is only defined up to a
+ * The SVD is a one-sided Jacobi iteration on the device (kernels_svd.hip) on X scaled by a power of two to max|X| ~ 1 (as
+ * Eigen's and LAPACK's SVDs scale), so any finite magnitude is handled.  A singular pair is only defined up to a
  * common sign:
  * method 0 does not depend on it, methods 1..3 do (in the reference as well -- they follow whatever Eigen's
  * BDCSVD returns), so for those only the construction from a given SVD is pinned by the tests. */
