@@ -35,7 +35,7 @@ VARIANTS = {
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
-SOURCES = ["kernels_stft.hip", "kernels_stft2.hip", "kernels_nmf.hip", "kernels_nmf5.hip", "kernels_nmf5_off.hip", "kernels_nmf_strip.hip", "kernels_nmf_bintile.hip", "kernels_nmf_wide.hip", "kernels_istft.hip", "kernels_feat.hip", "kernels_svd.hip", "kernels_range.hip", "api_core.hip", "api_corpus.hip", "api_algorithms.hip", "api_features.hip", "api_frames.hip", "api_pool.cpp"]
+SOURCES = ["kernels_stft.hip", "kernels_stft2.hip", "kernels_nmf.hip", "kernels_nmf5.hip", "kernels_nmf5_off.hip", "kernels_nmf_strip.hip", "kernels_nmf_bintile.hip", "kernels_nmf_wide.hip", "kernels_istft.hip", "kernels_feat.hip", "kernels_svd.hip", "kernels_range.hip", "api_core.hip", "api_corpus.hip", "api_algorithms.hip", "api_features.hip", "api_frames.hip", "api_pool.cpp", "kernels_nmfcross.hip", "api_cross.hip"]
 # kernel forms no production shape reaches are not part of the production library (kernels_nmf_bintile.hip was 415
 # lines of dead weight in lib/libflucoma_hip.so): compiled into the measurement builds only
 AB_ONLY = {"kernels_nmf_bintile.hip"}
@@ -58,7 +58,7 @@ def _newer(target, sources):
 # per-file extras: the factor-update kernels never see NaNs by construction (every operand is
 # clamped to >= eps or is a finite product of finite inputs), and fmax() without the sNaN
 # canonicalisation saves one op per quotient on the FP64 datapath the MFMAs share.
-EXTRA_FLAGS = {"kernels_nmf_wide.hip": ["-fno-honor-nans"], "kernels_nmf5.hip": ["-fno-honor-nans", "-Wno-inline-asm"], "kernels_nmf5_off.hip": ["-fno-honor-nans", "-Wno-inline-asm"], "kernels_nmf_strip.hip": ["-fno-honor-nans", "-mllvm", "-amdgpu-mfma-vgpr-form"], "kernels_nmf.hip": ["-fno-honor-nans"],
+EXTRA_FLAGS = {"kernels_nmf_wide.hip": ["-fno-honor-nans"], "kernels_nmfcross.hip": ["-ffp-contract=off"], "kernels_nmf5.hip": ["-fno-honor-nans", "-Wno-inline-asm"], "kernels_nmf5_off.hip": ["-fno-honor-nans", "-Wno-inline-asm"], "kernels_nmf_strip.hip": ["-fno-honor-nans", "-mllvm", "-amdgpu-mfma-vgpr-form"], "kernels_nmf.hip": ["-fno-honor-nans"],
                "kernels_nmf_bintile.hip": ["-fno-honor-nans", "-Wno-inline-asm", "-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
@@ -143,6 +143,26 @@ def build_host_tests() -> str:
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"g++ failed for client_driver:\n{r.stdout}\n{r.stderr}")
+        if r.stderr.strip():
+            sys.stderr.write(r.stderr)
+    build_nmfcross_driver()
+    return out
+
+
+def build_nmfcross_driver() -> str:
+    """g++ build of the BufNMFCross host-client test driver (tests/cpp/nmfcross_driver.cpp)."""
+    root = os.path.dirname(HERE)
+    src = os.path.join(root, "tests", "cpp", "nmfcross_driver.cpp")
+    out = os.path.join(LIBDIR, "nmfcross_driver")
+    deps = [src] + [os.path.join(root, "include", "flucoma_hip", f)
+                    for f in os.listdir(os.path.join(root, "include", "flucoma_hip"))]
+    deps.append(os.path.join(root, "include", "flucoma_hip.h"))
+    if _newer(out, deps) or _newer(out, [LIB]):
+        cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-pthread", src, "-o", out, "-L" + LIBDIR, "-lflucoma_hip",
+               "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib"]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"g++ failed for nmfcross_driver:\n{r.stdout}\n{r.stderr}")
         if r.stderr.strip():
             sys.stderr.write(r.stderr)
     return out

@@ -67,6 +67,7 @@ EXPORTS = [
     "fluhip_pool_create", "fluhip_pool_destroy", "fluhip_pool_size", "fluhip_pool_device", "fluhip_pool_last_error",
     "fluhip_pool_bufnmf_f32", "fluhip_pool_bufnmf_job_f32", "fluhip_pool_bufnmf_ragged_f32", "fluhip_pool_bufmfcc_f32",
     "fluhip_pool_bufmelbands_f32", "fluhip_shard_range", "fluhip_balanced_assignment", "fluhip_nmfmatch_f32", "fluhip_nmffilter_f32",
+    "fluhip_nmfcross_process_f64", "fluhip_griffinlim_f64", "fluhip_bufnmfcross_f32", "fluhip_debug_cross_plan",
 ]
 
 
@@ -125,6 +126,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                             ctypes.c_int, _fp, _ip]
     L.fluhip_bufstft_forward_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, _fp, _fp, _ip]
     L.fluhip_bufstft_inverse_f32.argtypes = [_vp, _fp, _fp, _i64, _i64, _i64, _i64, ctypes.c_int, _fp, _ip]
+    L.fluhip_nmfcross_process_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                              _dp, PROGRESS_FN, _vp]
+    L.fluhip_debug_cross_plan.argtypes = [_vp, _i64, _i64, _i64, _ip]
+    L.fluhip_griffinlim_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64]
+    L.fluhip_bufnmfcross_f32.argtypes = [_vp, _fp, _i64, _i64, _fp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                         _i64, _fp, PROGRESS_FN, _vp]
     L.fluhip_corpus_create.argtypes = [_vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
     L.fluhip_corpus_create_ragged.argtypes = [_vp, _i64, _ip, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
     L.fluhip_corpus_frames_of.argtypes = [_vp, _i64]
@@ -454,6 +461,53 @@ class Context:
         self._check(self.lib.fluhip_bufstft_inverse_f32(self.h, _f(mag), _f(phase), T, win, fft, hop, padding_mode,
                                                         _f(out), ctypes.byref(nout)))
         return out
+
+    # ---- BufNMFCross (alg/NMFCross.hpp, alg/GriffinLim.hpp, nrt/NMFCrossClient.hpp) ------------------------
+    def nmfcross_process(self, X, W0, time_sparsity=7, polyphony=11, continuity=7, iters=50, seed=42, progress=None):
+        """NMFCross::process: X [T,F] target magnitudes, W0 [K,F] source magnitudes (not modified) -> (H1 [T,K], status);
+        status is CANCELLED when the progress callback refused an iteration"""
+        X = np.asarray(X, dtype=np.float64)
+        W0 = np.asarray(W0, dtype=np.float64)
+        assert X.ndim == 2 and X.strides[1] == 8 and W0.ndim == 2 and W0.strides[1] == 8
+        T, F = X.shape
+        K = W0.shape[0]
+        assert W0.shape[1] == F
+        H1 = np.empty((T, K))
+        rc = self.lib.fluhip_nmfcross_process_f64(self.h, X.ctypes.data_as(_dp), T, F, X.strides[0] // 8,
+                                                  W0.ctypes.data_as(_dp), K, W0.strides[0] // 8, time_sparsity, polyphony,
+                                                  continuity, iters, seed, _d(H1), _cb(progress), None)
+        self._check(rc, allow=(OK, CANCELLED))
+        return H1, rc
+
+    def cross_plan(self, M, N, Kd):
+        """(big_tiles, splits, split_depth) of an NMFCross GEMM of an M x N output over Kd on this device"""
+        out = (_i64 * 3)()
+        self._check(self.lib.fluhip_debug_cross_plan(self.h, M, N, Kd, out))
+        return bool(out[0]), int(out[1]), int(out[2])
+
+    def griffinlim(self, spec, n_samples, win, fft, hop, iters=50, seed=42):
+        """GriffinLim::process on a complex [T,F] spectrum; returns the new spectrum"""
+        out = np.ascontiguousarray(spec, dtype=np.complex128).copy()
+        T, F = out.shape
+        self._check(self.lib.fluhip_griffinlim_f64(self.h, out.ctypes.data_as(_dp), T, F, n_samples, iters, win, fft, hop,
+                                                   seed))
+        return out
+
+    def bufnmfcross(self, source, target, win=1024, fft=-1, hop=-1, time_sparsity=7, polyphony=11, continuity=7, iters=50,
+                    seed=-1, progress=None, source_stride=1, target_stride=1):
+        """NMFCrossClient::process on channel 0 of two float buffers: returns (output [n_target] float32, status);
+        fft / hop < 0 take the FFTParams defaults (next power of two, win / 2)"""
+        w, h, f = _i64(), _i64(), _i64()
+        self._check(self.lib.fluhip_fft_params(win, hop, fft, ctypes.byref(w), ctypes.byref(h), ctypes.byref(f), None))
+        source = np.ascontiguousarray(source, dtype=np.float32)
+        target = np.ascontiguousarray(target, dtype=np.float32)
+        n_src, n_tgt = len(source) // source_stride, len(target) // target_stride
+        out = np.empty(max(n_tgt, 1), dtype=np.float32)
+        rc = self.lib.fluhip_bufnmfcross_f32(self.h, _f(source), n_src, source_stride, _f(target), n_tgt, target_stride,
+                                             w.value, f.value, h.value, time_sparsity, polyphony, continuity, iters, seed,
+                                             _f(out), _cb(progress), None)
+        self._check(rc, allow=(OK, CANCELLED))
+        return out[:n_tgt], rc
 
     # ---- profiling ----------------------------------------------------------------------
     def prof_enable(self, on=True):

@@ -31,7 +31,9 @@ extern "C" {
 
 /* 5 (round 6) = 4 + fluhip_last_error_is_out_of_memory, fluhip_clear_error (the host clients' batched -> channel-by-channel
  * fallback classifies by code: include/flucoma_hip/NMFClient.hpp needs them), fluhip_corpus_stft_mag_only,
- * fluhip_corpus_last_loop_ms, fluhip_debug_plan_shape, fluhip_debug_wnorm_form.  Nothing of version 4 changed meaning. */
+ * fluhip_corpus_last_loop_ms, fluhip_debug_plan_shape, fluhip_debug_wnorm_form.  Nothing of version 4 changed meaning.
+ * Added later within 5 (additive only): fluhip_nmfcross_process_f64, fluhip_griffinlim_f64, fluhip_bufnmfcross_f32,
+ * fluhip_debug_cross_plan. */
 #define FLUHIP_ABI_VERSION 5
 
 /* clients/common/Result.hpp:24  enum class Status { kOk, kWarning, kError, kCancelled } */
@@ -219,6 +221,39 @@ int fluhip_bufstft_forward_f32(fluhip_ctx* ctx, const float* audio, int64_t n, i
  * (call with out == NULL to query *n_out). */
 int fluhip_bufstft_inverse_f32(fluhip_ctx* ctx, const float* mag, const float* phase, int64_t hops, int64_t win,
                                int64_t fft, int64_t hop, int padding_mode, float* out, int64_t* n_out);
+
+/* ---- algorithm::NMFCross / GriffinLim, client::nmfcross::NMFCrossClient (BufNMFCross) ------------------------- */
+/* Added within version 5: these three exports are additive, nothing of the version-5 ABI changed meaning.
+ * NMFCross(iters) + addProgressCallback + process(X, H1, W0, r, p, c, seed)  (algorithms/public/NMFCross.hpp:46-78,
+ * 156-186): X T x F (ldx), W0 K x F (ldw, read only), H1 T x K.  1 <= p <= K, r, c >= 1.  progress(1..iters), returning 0
+ * cancels (FLUHIP_CANCELLED; the device is at most fluhip_ctx_set_progress_lag iterations ahead, 8 by default).
+ * The reference's constraint factor is 1 - ((i + 1) / iters) in INTEGER arithmetic (:132, :150): 1 on every iteration but
+ * the last and 0 on the last, so the temporal-sparsity and polyphony constraints leave H unchanged until iteration
+ * iters - 1 and there zero every entry they do not keep (with iters == 1: on iteration 0).  Reproduced as such.
+ * Polyphony ties (std::sort is not stable, :79-86) go to the lower source frame.  FP64 throughout; the quotients are
+ * correctly rounded divisions. */
+int fluhip_nmfcross_process_f64(fluhip_ctx* ctx, const double* X, int64_t T, int64_t F, int64_t ldx, const double* W0,
+                                int64_t K, int64_t ldw, int64_t time_sparsity, int64_t polyphony, int64_t continuity,
+                                int64_t iters, int64_t seed, double* H1, fluhip_progress_fn progress, void* user);
+/* GriffinLim::process (algorithms/public/GriffinLim.hpp:26-52): spec T x F interleaved complex, in and out;
+ * T == (n_samples + hop) / hop.  Hann window; the random phase is the reference's column-major T x F fill. */
+int fluhip_griffinlim_f64(fluhip_ctx* ctx, double* spec, int64_t T, int64_t F, int64_t n_samples, int64_t iters,
+                          int64_t win, int64_t fft, int64_t hop, int64_t seed);
+/* NMFCrossClient::process (clients/nrt/NMFCrossClient.hpp:84-184), channel 0 of each buffer, the whole job on the device:
+ * STFT of both, NMFCross with polyphony min(source frames, polyphony), synthesis, GriffinLim (50 iterations), ISTFT.
+ * out: n_tgt floats (the reference resizes its output to n_tgt x 1 at the SOURCE's sample rate).  The reference's
+ * messages in its order: "Empty source buffer", "Empty target buffer", "Time Sparsity is larger than target frames",
+ * "Continuity is larger than target frames".  progress(1..iters) in the loop, then iters+1 / +2 / +3 after synthesis /
+ * Griffin-Lim / ISTFT; returning 0 cancels (FLUHIP_CANCELLED, out unwritten). */
+int fluhip_bufnmfcross_f32(fluhip_ctx* ctx, const float* source, int64_t n_src, int64_t src_stride, const float* target,
+                           int64_t n_tgt, int64_t tgt_stride, int64_t win, int64_t fft, int64_t hop,
+                           int64_t time_sparsity, int64_t polyphony, int64_t continuity, int64_t iters, int64_t seed,
+                           float* out, fluhip_progress_fn progress, void* user);
+
+/* Diagnostic: the form the NMFCross GEMMs (GEMM1 T x F over K, GEMM2 T x K over F, synthesis T x 2F over K) take for an
+ * M x N output over a contraction of Kd on this context's device: out3 = {1: 128 x 128 workgroup tiles / 0: 64 x 64,
+ * contraction splits, split depth}.  What the tests assert the forms they exercise by. */
+int fluhip_debug_cross_plan(fluhip_ctx* ctx, int64_t M, int64_t N, int64_t Kd, int64_t* out3);
 
 /* ---- feature pipeline: BufMelBands / BufMFCC (BASELINE config 5) ------------------------------ */
 /* Replaces, for `count` equal-length mono buffers at once, the offline-wrapped real-time clients

@@ -14,6 +14,7 @@
 //
 //   nrt/NMFClient.hpp:54-71           nrt/NMFSeedClient.hpp:38-52       nrt/BufSTFTClient.hpp:36-47
 //   rt/MFCCClient.hpp:37-50, :171-173 rt/MelBandsClient.hpp:37-44, :151-153
+//   nrt/NMFCrossClient.hpp:38-48 (tests/golden/param_descriptors_nmfcross.json)
 //   rt/NMFFilterClient.hpp:34-38      rt/NMFMatchClient.hpp:32-38       (the two real-time clients behind the offline
 //                                                                        wrapper's parameters, as NMFFilterClient.hpp /
 //                                                                        NMFMatchClient.hpp here describe)
@@ -199,6 +200,18 @@ inline constexpr ParamDescriptor kBufNMFMatch[] = {
     inputBuffer("bases", "Bases Buffer"),
     longMin("maxComponents", "Maximum Number of Components", 20, 1),
     longMin("iterations", "Number of Iterations", 10, 1),
+    longParam("seed", "Random Seed", -1),
+    fft("fftSettings", "FFT Settings", 1024, -1, -1)};
+
+// nrt/NMFCrossClient.hpp:38-48
+inline constexpr ParamDescriptor kBufNMFCross[] = {
+    inputBuffer("source", "Source Buffer"),
+    inputBuffer("target", "Target Buffer"),
+    buffer("output", "Output Buffer"),
+    longMin("timeSparsity", "Time Sparsity", 7, 1, "Odd"),
+    longMin("polyphony", "Polyphony", 11, 1, "Odd, FrameSizeUpperLimit<fftSettings>"),
+    longMin("continuity", "Continuity", 7, 1, "Odd"),
+    longMin("iterations", "Number of Iterations", 50, 1),
     longParam("seed", "Random Seed", -1),
     fft("fftSettings", "FFT Settings", 1024, -1, -1)};
 

@@ -7,6 +7,7 @@ reference is compiled or copied -- and writes them as data, in the shape `tests/
 mirrors' tables (include/flucoma_hip/ParamDescriptors.hpp).  tests/test_client.py compares the two.
 
     python tools/make_param_descriptor_fixture.py [/root/reference] > tests/golden/param_descriptors.json
+    python tools/make_param_descriptor_fixture.py --nmfcross [/root/reference] > tests/golden/param_descriptors_nmfcross.json
 
 Offline clients the reference composes with makeNRTParams (BufMFCC, BufMelBands: rt/MFCCClient.hpp:171-173,
 rt/MelBandsClient.hpp:151-153) get the wrapper's parameters in front exactly as FluidNRTClientWrapper.hpp:33-39, :747-785
@@ -19,7 +20,8 @@ import os
 import re
 import sys
 
-REF = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
+_ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
+REF = _ARGS[0] if _ARGS else "/root/reference"
 INC = os.path.join(REF, "include", "flucoma", "clients")
 
 
@@ -117,6 +119,9 @@ def parse_entry(entry, index_names, param_names_by_index):
             if mm:
                 d[mm.group(1).lower()] = num(mm.group(2))
                 continue
+            if re.match(r"\w+\(\)$", c):          # a constraint without arguments (Odd())
+                rel.append(c[:-2])
+                continue
             mm = re.match(r"(\w+)<(\w+)>\(\)", c)
             if not mm:
                 raise ValueError("constraint? " + c)
@@ -165,6 +170,12 @@ def nrt_buffers(header):
     return [parse_entry(e, [], []) for e in split_top(text[s + 1:balanced(text, s) - 1])]
 
 
+def main_nmfcross():
+    """--nmfcross: tests/golden/param_descriptors_nmfcross.json, the table of nrt/NMFCrossClient.hpp (BufNMFCross)"""
+    json.dump({"BufNMFCross": table("nrt/NMFCrossClient.hpp")}, sys.stdout, indent=1)
+    sys.stdout.write("\n")
+
+
 def main():
     win = wrapper_inputs()
     pad = padding_param()
@@ -183,4 +194,7 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if "--nmfcross" in sys.argv:
+        main_nmfcross()
+    else:
+        main()
