@@ -340,9 +340,11 @@ int fluhip_nmf_process_frames_f64(fluhip_ctx* ctx, const double* X, int64_t T, i
 // ---------------------------------------------------------------------------------------
 // G: device [F][ldg], row f = bin f over the T frames (the transposed magnitude copy; destroyed).  Top factors
 // to the host: s [min(F,T)] descending, U [k][F] (row j = u_j), VT [k][T]; k from the coverage rule.
+// allPairs (fluhip_debug_jacobi_svd_f64): all min(F,T) pairs come back instead of the leading k; sweepsOut: the number of
+// sweeps the iteration took.
 static int nndsvd_device(fluhip_ctx* ctx, double* G, int64_t F, int64_t T, int64_t ldg, int64_t minRank, int64_t maxRank,
                          double amount, std::vector<double>& s, std::vector<double>& U, std::vector<double>& VT,
-                         int64_t* kOut)
+                         int64_t* kOut, bool allPairs = false, int64_t* sweepsOut = nullptr)
 {
   hipStream_t st = ctx->stream;
   DevBuf dJ, dN, dFlag;
@@ -363,6 +365,7 @@ static int nndsvd_device(fluhip_ctx* ctx, double* G, int64_t F, int64_t T, int64
                                        40, st);
   HIPCHK(ctx, hipGetLastError());
   if (sweeps < 0) return fail(ctx, "the SVD did not converge");
+  if (sweepsOut) *sweepsOut = sweeps;
   std::vector<double> norms((size_t) F);
   HIPCHK(ctx, hipMemcpyAsync(norms.data(), dN.p, (size_t) F * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
@@ -372,7 +375,7 @@ static int nndsvd_device(fluhip_ctx* ctx, double* G, int64_t F, int64_t T, int64
   const int64_t r = std::min(F, T);
   s.resize((size_t) r);
   for (int64_t i = 0; i < r; i++) s[(size_t) i] = norms[(size_t) order[(size_t) i]];
-  // alg/NNDSVD.hpp:47-58
+  // alg/NNDSVD.hpp:47-58.  A silent input has total == 0: 0 / 0 < amount is false there as here, so k = minRank.
   int64_t k = 0;
   if (amount == 0) k = minRank;
   else
@@ -385,9 +388,10 @@ static int nndsvd_device(fluhip_ctx* ctx, double* G, int64_t F, int64_t T, int64
   if (k > maxRank) k = maxRank;
   if (k > r) return fail(ctx, "rank above min(bins, frames)");
   *kOut = k;
-  U.assign((size_t) std::max<int64_t>(k, 1) * F, 0.0);
-  VT.assign((size_t) std::max<int64_t>(k, 1) * T, 0.0);
-  for (int64_t j = 0; j < k; j++)
+  const int64_t nd = allPairs ? r : k; // pairs that go to the host
+  U.assign((size_t) std::max<int64_t>(nd, 1) * F, 0.0);
+  VT.assign((size_t) std::max<int64_t>(nd, 1) * T, 0.0);
+  for (int64_t j = 0; j < nd; j++)
   {
     const int64_t row = order[(size_t) j];
     HIPCHK(ctx, hipMemcpyAsync(&U[(size_t) j * F], dJ.as<double>() + row * F, (size_t) F * sizeof(double),
@@ -395,7 +399,7 @@ static int nndsvd_device(fluhip_ctx* ctx, double* G, int64_t F, int64_t T, int64
     HIPCHK(ctx, hipMemcpyAsync(&VT[(size_t) j * T], G + row * ldg, (size_t) T * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   HIPCHK(ctx, hipStreamSynchronize(st));
-  for (int64_t j = 0; j < k; j++)
+  for (int64_t j = 0; j < nd; j++)
   {
     const double sj = s[(size_t) j];
     if (sj > 0)
@@ -481,6 +485,16 @@ static void nndsvd_construct(const std::vector<double>& s, const std::vector<dou
   }
 }
 
+// Methods 1..3 divide the positive / negative part of a singular pair by its norm (alg/NNDSVD.hpp:90-100): a pair whose
+// v is exactly zero (silence, or a rank above the matrix' own) is 0 / 0 there.  The reference writes the NaN; here it is
+// announced.
+static bool all_finite(const double* p, size_t n)
+{
+  for (size_t i = 0; i < n; i++)
+    if (!std::isfinite(p[i])) return false;
+  return true;
+}
+
 int fluhip_nndsvd_f64(fluhip_ctx* ctx, const double* X, int64_t T, int64_t F, int64_t ldx, int64_t w_rows,
                       int64_t min_rank, int64_t max_rank, double amount, int method, int64_t seed, double* W,
                       double* H, int64_t* rank_out)
@@ -506,8 +520,38 @@ int fluhip_nndsvd_f64(fluhip_ctx* ctx, const double* X, int64_t T, int64_t F, in
   for (int64_t t = 0; t < T; t++)
     for (int64_t f = 0; f < F; f++) mean += X[t * ldx + f];
   mean /= (double) (T * F);
-  nndsvd_construct(s, U, VT, F, T, k, w_rows, method, seed, mean, W, H);
+  // into host copies first: on the error below W, H and *rank_out are left as they were (like fluhip_bufnmfseed_f32)
+  std::vector<double> Wt((size_t) (w_rows * F)), Ht((size_t) (T * w_rows));
+  nndsvd_construct(s, U, VT, F, T, k, w_rows, method, seed, mean, Wt.data(), Ht.data());
+  if (!all_finite(Wt.data(), Wt.size()) || !all_finite(Ht.data(), Ht.size()))
+    return fail(ctx, "the factors are not finite: a singular pair of the rank asked for is zero (silent or rank-deficient input)");
+  std::copy(Wt.begin(), Wt.end(), W);
+  std::copy(Ht.begin(), Ht.end(), H);
   if (rank_out) *rank_out = k;
+  return FLUHIP_OK;
+}
+
+int fluhip_debug_jacobi_svd_f64(fluhip_ctx* ctx, const double* X, int64_t T, int64_t F, int64_t ldx, double* s_out,
+                                double* U_out, double* VT_out, int64_t* sweeps_out)
+{
+  if (!ctx) return FLUHIP_ERROR;
+  if (!X || !s_out || !U_out || !VT_out || T < 1 || F < 1 || ldx < F) return fail(ctx, "bad matrix arguments");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  DevBuf A, G;
+  HIPCHK(ctx, A.alloc((size_t) T * F * sizeof(double), false, st));
+  HIPCHK(ctx, G.alloc((size_t) F * T * sizeof(double), false, st));
+  HIPCHK(ctx, hipMemcpy2DAsync(A.p, (size_t) F * sizeof(double), X, (size_t) ldx * sizeof(double),
+                               (size_t) F * sizeof(double), (size_t) T, hipMemcpyHostToDevice, st));
+  launch_transpose(A.as<double>(), F, 0, G.as<double>(), T, 0, (int) T, (int) F, 1, st); // as fluhip_nndsvd_f64
+  std::vector<double> s, U, VT;
+  int64_t k = 0, sweeps = 0;
+  const int64_t r = std::min(F, T);
+  if (int rc = nndsvd_device(ctx, G.as<double>(), F, T, T, 0, r, 0.0, s, U, VT, &k, true, &sweeps)) return rc;
+  std::copy(s.begin(), s.end(), s_out);
+  std::copy(U.begin(), U.begin() + r * F, U_out);
+  std::copy(VT.begin(), VT.begin() + r * T, VT_out);
+  if (sweeps_out) *sweeps_out = sweeps;
   return FLUHIP_OK;
 }
 
@@ -551,14 +595,20 @@ int fluhip_bufnmfseed_f32(fluhip_ctx* ctx, const float* audio, int64_t n, int64_
   if (rc) return rc;
   std::vector<double> W((size_t) max_rank * F), H((size_t) T * max_rank);
   nndsvd_construct(s, U, VT, F, T, k, max_rank, method, seed, mean, W.data(), H.data());
-  // NMFSeedClient.hpp:108-128
+  // NMFSeedClient.hpp:108-128.  The reference scales the float envelopes by float(1 / max(H)) whatever the maximum: on
+  // silence (a maximum that is zero as a float, or whose reciprocal is not a float: the corpus path's silent bins are
+  // 1.5e-154, not 0) that is 0 * inf = NaN in every envelope it writes.  Announced here instead, before anything is written.
+  double maxH = H[0];
+  for (double v : H) maxH = std::max(maxH, v);
+  const float scale = (float) (1.0 / maxH);
+  if (!all_finite(W.data(), (size_t) (k * F)) || (acts_out && !all_finite(H.data(), H.size())))
+    return fail(ctx, "the factors are not finite: a singular pair of the rank asked for is zero (silent or rank-deficient input)");
+  if (acts_out && k > 0 && !((float) maxH > 0 && std::isfinite(scale))) // bases alone need no 1 / max
+    return fail(ctx, "silent input: the envelopes are all zero in single precision, 1 / max is undefined");
   if (bases_out)
     for (int64_t i = 0; i < max_rank * F; i++) bases_out[i] = i < k * F ? (float) W[(size_t) i] : 0.f;
   if (acts_out)
   {
-    double maxH = H[0];
-    for (double v : H) maxH = std::max(maxH, v);
-    const float scale = (float) (1.0 / maxH);
     for (int64_t j = 0; j < max_rank; j++)
       for (int64_t t = 0; t < T; t++)
         acts_out[j * T + t] = j < k ? (float) H[(size_t) t * max_rank + j] * scale : 0.f;

@@ -67,7 +67,7 @@ EXPORTS = [
     "fluhip_pool_create", "fluhip_pool_destroy", "fluhip_pool_size", "fluhip_pool_device", "fluhip_pool_last_error",
     "fluhip_pool_bufnmf_f32", "fluhip_pool_bufnmf_job_f32", "fluhip_pool_bufnmf_ragged_f32", "fluhip_pool_bufmfcc_f32",
     "fluhip_pool_bufmelbands_f32", "fluhip_shard_range", "fluhip_balanced_assignment", "fluhip_nmfmatch_f32", "fluhip_nmffilter_f32",
-    "fluhip_nmfcross_process_f64", "fluhip_griffinlim_f64", "fluhip_bufnmfcross_f32", "fluhip_debug_cross_plan",
+    "fluhip_nmfcross_process_f64", "fluhip_griffinlim_f64", "fluhip_bufnmfcross_f32", "fluhip_debug_cross_plan", "fluhip_debug_jacobi_svd_f64",
 ]
 
 
@@ -129,6 +129,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.fluhip_nmfcross_process_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                               _dp, PROGRESS_FN, _vp]
     L.fluhip_debug_cross_plan.argtypes = [_vp, _i64, _i64, _i64, _ip]
+    L.fluhip_debug_jacobi_svd_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _dp, _dp, _dp, _ip]
     L.fluhip_griffinlim_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64]
     L.fluhip_bufnmfcross_f32.argtypes = [_vp, _fp, _i64, _i64, _fp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                          _i64, _fp, PROGRESS_FN, _vp]
@@ -330,6 +331,19 @@ class Context:
         self._check(self.lib.fluhip_nndsvd_f64(self.h, X.ctypes.data_as(_dp), T, F, X.strides[0] // 8, w_rows, min_rank,
                                                max_rank, amount, method, seed, _d(W), _d(H), ctypes.byref(k)))
         return W, H, int(k.value)
+
+    def jacobi_svd(self, X):
+        """the SVD behind nndsvd / bufnmfseed, whole: s [r], U [r,F] (row j = u_j), VT [r,T] of X^T for X [T,F], and the
+        number of Jacobi sweeps; r = min(F, T)"""
+        X = np.asarray(X, dtype=np.float64)
+        assert X.ndim == 2 and X.strides[1] == 8
+        T, F = X.shape
+        r = min(T, F)
+        s, U, VT = np.empty(r), np.empty((r, F)), np.empty((r, T))
+        sweeps = ctypes.c_int64(0)
+        self._check(self.lib.fluhip_debug_jacobi_svd_f64(self.h, X.ctypes.data_as(_dp), T, F, X.strides[0] // 8, _d(s), _d(U),
+                                                         _d(VT), ctypes.byref(sweeps)))
+        return s, U, VT, int(sweeps.value)
 
     def bufnmfseed(self, audio, win, fft, hop, min_rank=1, max_rank=200, coverage=0.5, method=0, seed=-1, stride=1):
         """BufNMFSeed (nrt/NMFSeedClient.hpp): bases [max_rank,F] f32, activations [max_rank,T] f32, rank."""

@@ -33,7 +33,7 @@ extern "C" {
  * fallback classifies by code: include/flucoma_hip/NMFClient.hpp needs them), fluhip_corpus_stft_mag_only,
  * fluhip_corpus_last_loop_ms, fluhip_debug_plan_shape, fluhip_debug_wnorm_form.  Nothing of version 4 changed meaning.
  * Added later within 5 (additive only): fluhip_nmfcross_process_f64, fluhip_griffinlim_f64, fluhip_bufnmfcross_f32,
- * fluhip_debug_cross_plan. */
+ * fluhip_debug_cross_plan, fluhip_debug_jacobi_svd_f64. */
 #define FLUHIP_ABI_VERSION 5
 
 /* clients/common/Result.hpp:24  enum class Status { kOk, kWarning, kError, kCancelled } */
@@ -188,10 +188,22 @@ int fluhip_nndsvd_f64(fluhip_ctx* ctx, const double* X, int64_t T, int64_t F, in
                       double* H, int64_t* rank_out);
 /* Replaces NMFSeedClient::process (clients/nrt/NMFSeedClient.hpp:73-131; BufNMFSeed): STFT -> magnitude ->
  * NNDSVD -> bases (max_rank x F floats, rows >= rank untouched by the reference's resize-to-rank: here zero) and
- * activations (max_rank x T floats, scaled by 1 / max over the whole T x max_rank envelope matrix, :120-128). */
+ * activations (max_rank x T floats, scaled by 1 / max over the whole T x max_rank envelope matrix, :120-128).
+ * Silence: the reference's 1 / max is 1 / 0 and every envelope it writes NaN; here, when acts_out is asked for,
+ * FLUHIP_ERROR ("silent input ...").  With acts_out == NULL there is no 1 / max and silence gives its (finite) bases.
+ * Likewise, in both entry points, where methods 1..3 meet an exactly zero singular pair within the rank asked for (0 / 0
+ * in alg/NNDSVD.hpp:90-100): FLUHIP_ERROR instead of NaN factors.  On these errors neither entry point writes any of its
+ * outputs (W, H, bases_out, acts_out, *rank_out keep what they held). */
 int fluhip_bufnmfseed_f32(fluhip_ctx* ctx, const float* audio, int64_t n, int64_t stride, int64_t win,
                           int64_t fft, int64_t hop, int64_t min_rank, int64_t max_rank, double coverage,
                           int method, int64_t seed, float* bases_out, float* acts_out, int64_t* rank_out);
+
+/* Diagnostic: the SVD the two entry points above run, whole.  X: T x F with row stride ldx (any sign).  With r = min(F, T):
+ * s [r] descending, U [r x F] (row j = u_j), VT [r x T] with X^T = sum_j s_j u_j v_j^T, *sweeps_out (may be NULL) the
+ * number of Jacobi sweeps taken (the iteration gives up with FLUHIP_ERROR after 40).  The same upload, transpose, scaling,
+ * sweeps, sort and normalisation as fluhip_nndsvd_f64; the rows of VT that belong to an exactly zero s_j are zero. */
+int fluhip_debug_jacobi_svd_f64(fluhip_ctx* ctx, const double* X, int64_t T, int64_t F, int64_t ldx, double* s,
+                                double* U, double* VT, int64_t* sweeps_out);
 
 /* ---- client::bufnmf::NMFClient::process, one channel ---------------------------------- */
 /* Replaces the body of the channel loop, clients/nrt/NMFClient.hpp:240-300 (STFT -> magnitude
