@@ -35,7 +35,7 @@ VARIANTS = {
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
-SOURCES = ["kernels_stft.hip", "kernels_stft2.hip", "kernels_nmf.hip", "kernels_nmf5.hip", "kernels_nmf5_off.hip", "kernels_nmf_strip.hip", "kernels_nmf_bintile.hip", "kernels_nmf_wide.hip", "kernels_istft.hip", "kernels_feat.hip", "kernels_svd.hip", "kernels_range.hip", "api_core.hip", "api_corpus.hip", "api_algorithms.hip", "api_features.hip", "api_frames.hip", "api_pool.cpp", "kernels_nmfcross.hip", "api_cross.hip"]
+SOURCES = ["kernels_stft.hip", "kernels_stft2.hip", "kernels_nmf.hip", "kernels_nmf5.hip", "kernels_nmf5_off.hip", "kernels_nmf_strip.hip", "kernels_nmf_bintile.hip", "kernels_nmf_wide.hip", "kernels_istft.hip", "kernels_feat.hip", "kernels_svd.hip", "kernels_range.hip", "api_core.hip", "api_corpus.hip", "api_algorithms.hip", "api_features.hip", "api_frames.hip", "api_pool.cpp", "kernels_nmfcross.hip", "api_cross.hip", "kernels_novelty.hip", "api_novelty.hip"]
 # kernel forms no production shape reaches are not part of the production library (kernels_nmf_bintile.hip was 415
 # lines of dead weight in lib/libflucoma_hip.so): compiled into the measurement builds only
 AB_ONLY = {"kernels_nmf_bintile.hip"}
@@ -146,14 +146,24 @@ def build_host_tests() -> str:
         if r.stderr.strip():
             sys.stderr.write(r.stderr)
     build_nmfcross_driver()
+    build_novelty_driver()
     return out
 
 
 def build_nmfcross_driver() -> str:
     """g++ build of the BufNMFCross host-client test driver (tests/cpp/nmfcross_driver.cpp)."""
+    return _build_driver("nmfcross_driver")
+
+
+def build_novelty_driver() -> str:
+    """g++ build of the BufNoveltySlice / BufNoveltyFeature host-client test driver (tests/cpp/novelty_driver.cpp)."""
+    return _build_driver("novelty_driver")
+
+
+def _build_driver(name: str) -> str:
     root = os.path.dirname(HERE)
-    src = os.path.join(root, "tests", "cpp", "nmfcross_driver.cpp")
-    out = os.path.join(LIBDIR, "nmfcross_driver")
+    src = os.path.join(root, "tests", "cpp", name + ".cpp")
+    out = os.path.join(LIBDIR, name)
     deps = [src] + [os.path.join(root, "include", "flucoma_hip", f)
                     for f in os.listdir(os.path.join(root, "include", "flucoma_hip"))]
     deps.append(os.path.join(root, "include", "flucoma_hip.h"))
@@ -162,7 +172,7 @@ def build_nmfcross_driver() -> str:
                "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib"]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
-            raise RuntimeError(f"g++ failed for nmfcross_driver:\n{r.stdout}\n{r.stderr}")
+            raise RuntimeError(f"g++ failed for {name}:\n{r.stdout}\n{r.stderr}")
         if r.stderr.strip():
             sys.stderr.write(r.stderr)
     return out

@@ -2,6 +2,62 @@
 // (algorithms/public/MelBands.hpp, DCT.hpp; clients/rt/MFCCClient.hpp, MelBandsClient.hpp behind StreamingControl) of the C ABI.
 #include "api_internal.h"
 
+// the host-side tables of the mel / DCT kernels: dense bin-major filter bank, the same packed over each band's support, DCT rows
+void MelTables::build(bool mfcc, int64_t F, int64_t nBands, int64_t bandsPad, int64_t nCoefs, int64_t startCoeff, double minFreq,
+                      double maxFreq, double sampleRate)
+{
+  // mel filter bank (alg/MelBands.hpp:53-73), bin-major and zero padded; f64 on the host like the reference
+  filtT.assign((size_t) F * bandsPad, 0.0);
+  {
+    auto hz2mel = [](double x) { return 1127.01048 * std::log(x / 700.0 + 1.0); };
+    const int64_t nc = nBands + 2;
+    std::vector<double> centres((size_t) nc);
+    const double mlo = hz2mel(minFreq), mhi = hz2mel(maxFreq);
+    for (int64_t i = 0; i < nc; i++)
+      centres[(size_t) i] = 700.0 * (std::exp((mlo + (double) i * (mhi - mlo) / (double) (nc - 1)) / 1127.01048) - 1.0);
+    for (int64_t b = 0; b < nBands; b++)
+    {
+      const double d0 = std::fabs(centres[(size_t) b] - centres[(size_t) b + 1]);
+      const double d1 = std::fabs(centres[(size_t) b + 1] - centres[(size_t) b + 2]);
+      for (int64_t f = 0; f < F; f++)
+      {
+        const double hz = (double) f * (sampleRate / 2.0) / (double) (F - 1);
+        const double lower = -(centres[(size_t) b] - hz) / d0, upper = (centres[(size_t) b + 2] - hz) / d1;
+        filtT[(size_t) (f * bandsPad + b)] = std::max(0.0, std::min(lower, upper));
+      }
+    }
+  }
+  // the filter bank over each band's support only (kernels_feat.hip): first non-zero bin and packed weights
+  bandLo.assign((size_t) bandsPad, 0);
+  maxLen = 1;
+  {
+    std::vector<int64_t> hi((size_t) bandsPad, -1);
+    for (int64_t b = 0; b < nBands; b++)
+    {
+      int64_t lo = -1;
+      for (int64_t f = 0; f < F; f++)
+        if (filtT[(size_t) (f * bandsPad + b)] != 0.0) { if (lo < 0) lo = f; hi[(size_t) b] = f; }
+      bandLo[(size_t) b] = (int) std::max<int64_t>(lo, 0);
+      if (lo >= 0) maxLen = std::max(maxLen, hi[(size_t) b] - lo + 1);
+    }
+  }
+  wpack.assign((size_t) maxLen * bandsPad, 0.0);
+  for (int64_t b = 0; b < nBands; b++)
+    for (int64_t j = 0; j < maxLen; j++)
+    {
+      const int64_t f = bandLo[(size_t) b] + j;
+      if (f < F) wpack[(size_t) (j * bandsPad + b)] = filtT[(size_t) (f * bandsPad + b)];
+    }
+  nDct = mfcc ? std::min(nCoefs + startCoeff, nBands) : 0; // rt/MFCCClient.hpp:104-105
+  dct.assign((size_t) std::max<int64_t>(1, nDct * nBands), 0.0);
+  for (int64_t i = 0; i < nDct; i++) // alg/DCT.hpp:53-61
+  {
+    const double scale = i == 0 ? 1.0 / std::sqrt((double) nBands) : std::sqrt(2.0 / (double) nBands);
+    for (int64_t j = 0; j < nBands; j++)
+      dct[(size_t) (i * nBands + j)] = std::cos((M_PI / (double) nBands) * (double) i * (0.5 + (double) j)) * scale;
+  }
+}
+
 extern "C" {
 
 // ---- BufSTFT ------------------------------------------------------------------
@@ -139,56 +195,11 @@ static int features_common(fluhip_ctx* ctx, bool mfcc, const float* audio, int64
   if (frames_out) *frames_out = T;
   const int64_t Tp = round_up(T, 32), Fp = round_up(F, 32);
   const int64_t bandsPad = round_up(nBands, 64);
-  // mel filter bank (alg/MelBands.hpp:53-73), bin-major and zero padded; f64 on the host like the reference
-  std::vector<double> filtT((size_t) F * bandsPad, 0.0);
-  {
-    auto hz2mel = [](double x) { return 1127.01048 * std::log(x / 700.0 + 1.0); };
-    const int64_t nc = nBands + 2;
-    std::vector<double> centres((size_t) nc);
-    const double mlo = hz2mel(minFreq), mhi = hz2mel(maxFreq);
-    for (int64_t i = 0; i < nc; i++)
-      centres[(size_t) i] = 700.0 * (std::exp((mlo + (double) i * (mhi - mlo) / (double) (nc - 1)) / 1127.01048) - 1.0);
-    for (int64_t b = 0; b < nBands; b++)
-    {
-      const double d0 = std::fabs(centres[(size_t) b] - centres[(size_t) b + 1]);
-      const double d1 = std::fabs(centres[(size_t) b + 1] - centres[(size_t) b + 2]);
-      for (int64_t f = 0; f < F; f++)
-      {
-        const double hz = (double) f * (sampleRate / 2.0) / (double) (F - 1);
-        const double lower = -(centres[(size_t) b] - hz) / d0, upper = (centres[(size_t) b + 2] - hz) / d1;
-        filtT[(size_t) (f * bandsPad + b)] = std::max(0.0, std::min(lower, upper));
-      }
-    }
-  }
-  // the filter bank over each band's support only (kernels_feat.hip): first non-zero bin and packed weights
-  std::vector<int> bandLo((size_t) bandsPad, 0);
-  int64_t maxLen = 1;
-  {
-    std::vector<int64_t> hi((size_t) bandsPad, -1);
-    for (int64_t b = 0; b < nBands; b++)
-    {
-      int64_t lo = -1;
-      for (int64_t f = 0; f < F; f++)
-        if (filtT[(size_t) (f * bandsPad + b)] != 0.0) { if (lo < 0) lo = f; hi[(size_t) b] = f; }
-      bandLo[(size_t) b] = (int) std::max<int64_t>(lo, 0);
-      if (lo >= 0) maxLen = std::max(maxLen, hi[(size_t) b] - lo + 1);
-    }
-  }
-  std::vector<double> wpack((size_t) maxLen * bandsPad, 0.0);
-  for (int64_t b = 0; b < nBands; b++)
-    for (int64_t j = 0; j < maxLen; j++)
-    {
-      const int64_t f = bandLo[(size_t) b] + j;
-      if (f < F) wpack[(size_t) (j * bandsPad + b)] = filtT[(size_t) (f * bandsPad + b)];
-    }
-  const int64_t nDct = mfcc ? std::min(nCoefs + startCoeff, nBands) : 0; // rt/MFCCClient.hpp:104-105
-  std::vector<double> dct((size_t) std::max<int64_t>(1, nDct * nBands));
-  for (int64_t i = 0; i < nDct; i++) // alg/DCT.hpp:53-61
-  {
-    const double scale = i == 0 ? 1.0 / std::sqrt((double) nBands) : std::sqrt(2.0 / (double) nBands);
-    for (int64_t j = 0; j < nBands; j++)
-      dct[(size_t) (i * nBands + j)] = std::cos((M_PI / (double) nBands) * (double) i * (0.5 + (double) j)) * scale;
-  }
+  MelTables mel;
+  mel.build(mfcc, F, nBands, bandsPad, nCoefs, startCoeff, minFreq, maxFreq, sampleRate);
+  const std::vector<double>&filtT = mel.filtT, &wpack = mel.wpack, &dct = mel.dct;
+  const std::vector<int>& bandLo = mel.bandLo;
+  const int64_t maxLen = mel.maxLen, nDct = mel.nDct;
   const int64_t nOut = mfcc ? nCoefs : nBands;
   const double *wtab = nullptr, *ttab = nullptr;
   rc = get_window(ctx, win, fft, FLUHIP_WINDOW_HANN, &wtab);

@@ -337,6 +337,18 @@ void draw_uniform(int64_t seed, size_t count, std::vector<double>& out);
 int corpus_init_factors(fluhip_corpus* c, int64_t seed, const int64_t* seeds, const FactorInit& fi);
 int corpus_iterate(fluhip_corpus* c, int64_t iters, bool updateW, bool updateH, fluhip_progress_fn progress, void* user);
 
+// api_features.hip
+struct MelTables
+{
+  std::vector<double> filtT; // [F][bandsPad]
+  std::vector<int> bandLo;   // [bandsPad]
+  std::vector<double> wpack; // [maxLen][bandsPad]
+  std::vector<double> dct;   // [nDct][nBands]
+  int64_t maxLen = 1, nDct = 0;
+  void build(bool mfcc, int64_t F, int64_t nBands, int64_t bandsPad, int64_t nCoefs, int64_t startCoeff, double minFreq,
+             double maxFreq, double sampleRate);
+};
+
 // api_algorithms.hip
 int process_frames_on_device(fluhip_ctx* ctx, fluhip_corpus& c, const double* W0host, int64_t iters, int64_t seed);
 

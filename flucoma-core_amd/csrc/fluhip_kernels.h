@@ -361,6 +361,9 @@ struct FeatArgs
   int nDct, startCoeff;
   int nOut;             // features per frame written (nBands, or nCoefs)
   float* out;           // [B][nOut][T]
+  // launch_features only: when set, the MFCC coefficients leave unrounded and frame-major, [B][T][nOut] doubles, and
+  // `out` is not written (the feature rows of the novelty curve)
+  double* out64 = nullptr;
 };
 void launch_features(const FeatArgs& a, hipStream_t s);
 // fused form (kernels_stft2.hip): STFT -> mel bands [-> DCT] without the magnitudes leaving the chip.  up / dn / slot

@@ -132,7 +132,11 @@ __global__ __launch_bounds__(256) void mel_kernel(FeatArgs a)
       const double* drow = a.dct + (int64_t) (a.startCoeff + j) * a.nBands;
       for (int band = 0; band < a.nBands; band++) s += drow[band] * wl[i * a.bandsPad + band]; // alg/DCT.hpp:73-75
     }
-    if (t0 + i < a.T) a.out[((int64_t) b * a.nOut + j) * a.T + t0 + i] = (float) s;
+    if (t0 + i < a.T)
+    {
+      if (a.out64) a.out64[((int64_t) b * a.T + t0 + i) * a.nOut + j] = s;
+      else a.out[((int64_t) b * a.nOut + j) * a.T + t0 + i] = (float) s;
+    }
   }
 }
 

@@ -68,6 +68,8 @@ EXPORTS = [
     "fluhip_pool_bufnmf_f32", "fluhip_pool_bufnmf_job_f32", "fluhip_pool_bufnmf_ragged_f32", "fluhip_pool_bufmfcc_f32",
     "fluhip_pool_bufmelbands_f32", "fluhip_shard_range", "fluhip_balanced_assignment", "fluhip_nmfmatch_f32", "fluhip_nmffilter_f32",
     "fluhip_nmfcross_process_f64", "fluhip_griffinlim_f64", "fluhip_bufnmfcross_f32", "fluhip_debug_cross_plan", "fluhip_debug_jacobi_svd_f64",
+    "fluhip_novelty_curve_f64", "fluhip_novelty_slices_f64", "fluhip_bufnoveltyslice_f32", "fluhip_bufnoveltyfeature_f32",
+    "fluhip_debug_novelty_plan",
 ]
 
 
@@ -133,6 +135,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.fluhip_griffinlim_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64]
     L.fluhip_bufnmfcross_f32.argtypes = [_vp, _fp, _i64, _i64, _fp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                          _i64, _fp, PROGRESS_FN, _vp]
+    _u8p = ctypes.POINTER(ctypes.c_ubyte)
+    L.fluhip_novelty_curve_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _dp]
+    L.fluhip_novelty_slices_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _dbl, _i64, _u8p, _ip, _dp]
+    L.fluhip_bufnoveltyslice_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, ctypes.c_int, _i64, _dbl, _i64, _i64, _i64,
+                                             _i64, _i64, _dbl, _ip, _i64, _ip]
+    L.fluhip_bufnoveltyfeature_f32.argtypes = [_vp, _fp, _i64, _i64, ctypes.c_int, _i64, _i64, _i64, _i64, _i64, _dbl,
+                                               ctypes.c_int, _fp, _ip]
+    L.fluhip_debug_novelty_plan.argtypes = [_vp, _i64, _i64, _i64, _ip]
     L.fluhip_corpus_create.argtypes = [_vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
     L.fluhip_corpus_create_ragged.argtypes = [_vp, _i64, _ip, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
     L.fluhip_corpus_frames_of.argtypes = [_vp, _i64]
@@ -522,6 +532,83 @@ class Context:
                                              _f(out), _cb(progress), None)
         self._check(rc, allow=(OK, CANCELLED))
         return out[:n_tgt], rc
+
+    # ---- BufNoveltySlice / BufNoveltyFeature (util/Novelty.hpp, NoveltyFeature.hpp, NoveltySegmentation.hpp) ------------
+    @staticmethod
+    def _novelty_feat(feat):
+        feat = np.asarray(feat, dtype=np.float64)
+        if feat.ndim == 2:
+            feat = feat[None]
+        assert feat.ndim == 3 and feat.strides[2] == 8
+        count, T, D = feat.shape
+        ld = feat.strides[1] // 8
+        assert count == 1 or feat.strides[0] == T * ld * 8, "buffers must lie T rows apart"
+        return feat, count, T, D, ld
+
+    def novelty_curve(self, feat, kernel_size=3, filter_size=1):
+        """NoveltyFeature::processFrame over all frames: feat [count,T,D] (or [T,D]; rows may be strided) -> curve [count,T]"""
+        feat, count, T, D, ld = self._novelty_feat(feat)
+        curve = np.empty((count, T))
+        self._check(self.lib.fluhip_novelty_curve_f64(self.h, feat.ctypes.data_as(_dp), count, T, D, ld, kernel_size,
+                                                      filter_size, _d(curve)))
+        return curve
+
+    def novelty_slices(self, feat, kernel_size=3, filter_size=1, threshold=0.5, min_slice=2):
+        """NoveltySegmentation::processFrame over all frames -> (det [count,T] uint8, counts [count], curve [count,T])"""
+        feat, count, T, D, ld = self._novelty_feat(feat)
+        curve = np.empty((count, T))
+        det = np.empty((count, T), dtype=np.uint8)
+        counts = np.empty(count, dtype=np.int64)
+        self._check(self.lib.fluhip_novelty_slices_f64(self.h, feat.ctypes.data_as(_dp), count, T, D, ld, kernel_size,
+                                                       filter_size, threshold, min_slice,
+                                                       det.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)),
+                                                       counts.ctypes.data_as(_ip), _d(curve)))
+        return det, counts, curve
+
+    def novelty_plan(self, T, D, kernel_size):
+        """(form, rows held, curve values written) per workgroup: form 0 MFMA on chip, 1 FMAs on chip, 2 tiled"""
+        out = (_i64 * 3)()
+        self._check(self.lib.fluhip_debug_novelty_plan(self.h, T, D, kernel_size, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def bufnoveltyslice(self, audio, algorithm=0, kernel_size=3, threshold=0.5, filter_size=1, min_slice=2, win=1024,
+                        fft=-1, hop=-1, sr=44100.0, start_frame=0, capacity=None):
+        """NRTNoveltySliceClient on audio [count,channels,n] (or [channels,n] / [n]): a list of int64 index arrays, one per
+        buffer ([-1] when nothing was detected).  capacity: values kept per buffer (default: every possible frame)"""
+        w, h, f = _i64(), _i64(), _i64()
+        self._check(self.lib.fluhip_fft_params(win, hop, fft, ctypes.byref(w), ctypes.byref(h), ctypes.byref(f), None))
+        audio = np.asarray(audio, dtype=np.float32)
+        while audio.ndim < 3:
+            audio = audio[None]
+        audio = np.ascontiguousarray(audio)
+        count, channels, n = audio.shape
+        if capacity is None:
+            capacity = n // h.value + 2
+        idx = np.full((count, max(capacity, 1)), -2, dtype=np.int64)
+        counts = np.zeros(count, dtype=np.int64)
+        self._check(self.lib.fluhip_bufnoveltyslice_f32(self.h, _f(audio), count, channels, n, start_frame, algorithm,
+                                                        kernel_size, threshold, filter_size, min_slice, w.value, f.value,
+                                                        h.value, sr, idx.ctypes.data_as(_ip), capacity,
+                                                        counts.ctypes.data_as(_ip)))
+        self.last_slice_counts = counts
+        return [idx[b, :min(int(counts[b]), capacity)].copy() for b in range(count)]
+
+    def bufnoveltyfeature(self, audio, algorithm=0, kernel_size=3, filter_size=1, win=1024, fft=-1, hop=-1, sr=44100.0,
+                          padding_mode=1):
+        """NRTNoveltyFeatureClient on mono buffers [count,n] (or [n]) -> float32 [count,frames]"""
+        w, h, f = _i64(), _i64(), _i64()
+        self._check(self.lib.fluhip_fft_params(win, hop, fft, ctypes.byref(w), ctypes.byref(h), ctypes.byref(f), None))
+        audio = np.ascontiguousarray(np.atleast_2d(audio), dtype=np.float32)
+        count, n = audio.shape
+        Tr = _i64(0)
+        self._check(self.lib.fluhip_bufnoveltyfeature_f32(self.h, _f(audio), count, n, algorithm, kernel_size, filter_size,
+                                                          w.value, f.value, h.value, sr, padding_mode, None,
+                                                          ctypes.byref(Tr)))
+        out = np.empty((count, Tr.value), dtype=np.float32)
+        self._check(self.lib.fluhip_bufnoveltyfeature_f32(self.h, _f(audio), count, n, algorithm, kernel_size, filter_size,
+                                                          w.value, f.value, h.value, sr, padding_mode, _f(out),
+                                                          ctypes.byref(Tr)))
+        return out
 
     # ---- profiling ----------------------------------------------------------------------
     def prof_enable(self, on=True):

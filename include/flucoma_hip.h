@@ -33,7 +33,8 @@ extern "C" {
  * fallback classifies by code: include/flucoma_hip/NMFClient.hpp needs them), fluhip_corpus_stft_mag_only,
  * fluhip_corpus_last_loop_ms, fluhip_debug_plan_shape, fluhip_debug_wnorm_form.  Nothing of version 4 changed meaning.
  * Added later within 5 (additive only): fluhip_nmfcross_process_f64, fluhip_griffinlim_f64, fluhip_bufnmfcross_f32,
- * fluhip_debug_cross_plan, fluhip_debug_jacobi_svd_f64. */
+ * fluhip_debug_cross_plan, fluhip_debug_jacobi_svd_f64, fluhip_novelty_curve_f64, fluhip_novelty_slices_f64,
+ * fluhip_bufnoveltyslice_f32, fluhip_bufnoveltyfeature_f32, fluhip_debug_novelty_plan. */
 #define FLUHIP_ABI_VERSION 5
 
 /* clients/common/Result.hpp:24  enum class Status { kOk, kWarning, kError, kCancelled } */
@@ -266,6 +267,54 @@ int fluhip_bufnmfcross_f32(fluhip_ctx* ctx, const float* source, int64_t n_src, 
  * M x N output over a contraction of Kd on this context's device: out3 = {1: 128 x 128 workgroup tiles / 0: 64 x 64,
  * contraction splits, split depth}.  What the tests assert the forms they exercise by. */
 int fluhip_debug_cross_plan(fluhip_ctx* ctx, int64_t M, int64_t N, int64_t Kd, int64_t* out3);
+
+/* ---- algorithm::Novelty / NoveltyFeature / NoveltySegmentation, clients BufNoveltySlice / BufNoveltyFeature ---- */
+/* Added within version 5 (additive).  FP64 throughout, every buffer of a call in the same launches.
+ * kernel_size odd and >= 3 (at most 32767), 1 <= filter_size <= 1048576, threshold >= 0, min_slice >= 0: anything else
+ * is FLUHIP_ERROR with a message and no output written.
+ *
+ * NoveltyFeature::processFrame over all frames (algorithms/public/NoveltyFeature.hpp:44-62 on util/Novelty.hpp:48-100):
+ * feat `count` x T x D doubles (row stride ld >= D, buffer stride T ld) -> curve count x T.  filter_size 1 gives the raw
+ * Novelty::processFrame output.  The gaussian of the checkerboard kernel has sigma = kernel_size / 3 in INTEGER
+ * arithmetic, as the reference's (algorithms/public/WindowFuncs.hpp:66-73).  feat and curve may both be device
+ * pointers: they are then used in place. */
+int fluhip_novelty_curve_f64(fluhip_ctx* ctx, const double* feat, int64_t count, int64_t T, int64_t D, int64_t ld,
+                             int64_t kernel_size, int64_t filter_size, double* curve);
+/* NoveltySegmentation::processFrame over all frames (algorithms/public/NoveltySegmentation.hpp:44-63): det count x T
+ * bytes (1 where the call for that frame returns a detection -- one frame behind the peak it reports), counts [count]
+ * detections per buffer; curve (count x T, may be NULL) as above. */
+int fluhip_novelty_slices_f64(fluhip_ctx* ctx, const double* feat, int64_t count, int64_t T, int64_t D, int64_t ld,
+                              int64_t kernel_size, int64_t filter_size, double threshold, int64_t min_slice,
+                              unsigned char* det, int64_t* counts, double* curve);
+/* NRTNoveltySliceClient (clients/rt/NoveltySliceClient.hpp behind NRTSliceAdaptor, clients/common/
+ * FluidNRTClientWrapper.hpp:665-725, SpikesToTimes.hpp) for `count` equal-length buffers: audio [count][channels][n]
+ * floats, the channels summed in float; frame i holds the samples [i hop - win, i hop) of the sum followed by zeros
+ * (FluidSource / BufferedProcess at the wrapper's host vector of 64), a detection of frame i stands at sample i hop;
+ * detections inside the first latency = hop (1 + ((kernel_size + 1) >> 1) + (filter_size rounded up to even >> 1))
+ * samples become ONE at 0, the others are reported as sample - latency + start_frame while below n.
+ * algorithm: 0 Spectrum (STFT magnitudes, D = fft / 2 + 1), 1 MFCC (40 mel bands 20 Hz .. 20 kHz, 13 coefficients from
+ * c0, in double).  2 Chroma, 3 Pitch, 4 Loudness are NOT built: FLUHIP_ERROR, the message names the algorithm, nothing
+ * is written.  indices [count][capacity], counts [count] = the TRUE number of values of each buffer (values past
+ * `capacity` are not written); a buffer without detection has count 1 and the single value -1.  Silence gives that for
+ * Spectrum.  For MFCC it gives ONE slice at start_frame, as the reference's arithmetic does: the MFCC rows of silence
+ * are constant and non-zero (20 log10(eps) in every band) against the zeros the ring of frames starts with, the curve
+ * peaks at frame 1 (0.857 at kernel_size 3), inside the latency.
+ * filter_size is at most 1048576 here. */
+int fluhip_bufnoveltyslice_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t channels, int64_t n,
+                               int64_t start_frame, int algorithm, int64_t kernel_size, double threshold,
+                               int64_t filter_size, int64_t min_slice, int64_t win, int64_t fft, int64_t hop,
+                               double sample_rate, int64_t* indices, int64_t capacity, int64_t* counts);
+/* NRTNoveltyFeatureClient (clients/rt/NoveltyFeatureClient.hpp behind StreamingControl, FluidNRTClientWrapper.hpp:551-660)
+ * for `count` equal-length mono buffers: one float per hop, the first latency / hop values dropped; padding_mode
+ * 0 / 1 / 2 as the other *_padded_* calls.  out [count][*frames_out] (out == NULL: only *frames_out is set).
+ * algorithm as above. */
+int fluhip_bufnoveltyfeature_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int algorithm,
+                                 int64_t kernel_size, int64_t filter_size, int64_t win, int64_t fft, int64_t hop,
+                                 double sample_rate, int padding_mode, float* out, int64_t* frames_out);
+/* Diagnostic: how the novelty curve of T frames of D dimensions is computed at a kernel size: out3 = {form, feature rows
+ * a workgroup holds, curve values it writes}; form 0: band on chip, Gram blocks on the FP64 matrix pipe; 1: band on chip,
+ * plain FMAs (D < 32); 2: tiled through a workspace in memory (kernel_size > 65). */
+int fluhip_debug_novelty_plan(fluhip_ctx* ctx, int64_t T, int64_t D, int64_t kernel_size, int64_t* out3);
 
 /* ---- feature pipeline: BufMelBands / BufMFCC (BASELINE config 5) ------------------------------ */
 /* Replaces, for `count` equal-length mono buffers at once, the offline-wrapped real-time clients

@@ -15,6 +15,7 @@
 //   nrt/NMFClient.hpp:54-71           nrt/NMFSeedClient.hpp:38-52       nrt/BufSTFTClient.hpp:36-47
 //   rt/MFCCClient.hpp:37-50, :171-173 rt/MelBandsClient.hpp:37-44, :151-153
 //   nrt/NMFCrossClient.hpp:38-48 (tests/golden/param_descriptors_nmfcross.json)
+//   rt/NoveltySliceClient.hpp:44-53, rt/NoveltyFeatureClient.hpp:36-43 (tests/golden/param_descriptors_novelty.json)
 //   rt/NMFFilterClient.hpp:34-38      rt/NMFMatchClient.hpp:32-38       (the two real-time clients behind the offline
 //                                                                        wrapper's parameters, as NMFFilterClient.hpp /
 //                                                                        NMFMatchClient.hpp here describe)
@@ -213,6 +214,37 @@ inline constexpr ParamDescriptor kBufNMFCross[] = {
     longMin("continuity", "Continuity", 7, 1, "Odd"),
     longMin("iterations", "Number of Iterations", 50, 1),
     longParam("seed", "Random Seed", -1),
+    fft("fftSettings", "FFT Settings", 1024, -1, -1)};
+
+inline constexpr const char* kNoveltyAlgorithms[] = {"Spectrum", "MFCC", "Chroma", "Pitch", "Loudness"};
+
+// the slicing wrapper's parameters (cc/FluidNRTClientWrapper.hpp:33-39) and "indices", then rt/NoveltySliceClient.hpp:44-53
+inline constexpr ParamDescriptor kBufNoveltySlice[] = {
+    inputBuffer("source", "Source Buffer"),
+    longMin("startFrame", "Source Offset", 0, 0),
+    longParam("numFrames", "Number of Frames", -1),
+    longMin("startChan", "Start Channel", 0, 0),
+    longParam("numChans", "Number of Channels", -1),
+    buffer("indices", "Indices Buffer"),
+    enumParam("algorithm", "Algorithm for Feature Extraction", 0, kNoveltyAlgorithms),
+    longMin("kernelSize", "KernelSize", 3, 3, "Odd"),
+    floatMin("threshold", "Threshold", 0.5, 0),
+    longMin("filterSize", "Smoothing Filter Size", 1, 1),
+    longMin("minSliceLength", "Minimum Length of Slice", 2, 0),
+    fft("fftSettings", "FFT Settings", 1024, -1, -1)};
+
+// the control wrapper's parameters, then rt/NoveltyFeatureClient.hpp:36-43
+inline constexpr ParamDescriptor kBufNoveltyFeature[] = {
+    inputBuffer("source", "Source Buffer"),
+    longMin("startFrame", "Source Offset", 0, 0),
+    longParam("numFrames", "Number of Frames", -1),
+    longMin("startChan", "Start Channel", 0, 0),
+    longParam("numChans", "Number of Channels", -1),
+    buffer("features", "Feature Buffer"),
+    enumParam("padding", "Added Padding", 1, kPaddingModes),
+    enumParam("algorithm", "Algorithm for Feature Extraction", 0, kNoveltyAlgorithms),
+    longMin("kernelSize", "KernelSize", 3, 3, "Odd"),
+    longMin("filterSize", "Smoothing Filter Size", 1, 1),
     fft("fftSettings", "FFT Settings", 1024, -1, -1)};
 
 template <std::size_t N>

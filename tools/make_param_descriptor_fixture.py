@@ -8,6 +8,7 @@ mirrors' tables (include/flucoma_hip/ParamDescriptors.hpp).  tests/test_client.p
 
     python tools/make_param_descriptor_fixture.py [/root/reference] > tests/golden/param_descriptors.json
     python tools/make_param_descriptor_fixture.py --nmfcross [/root/reference] > tests/golden/param_descriptors_nmfcross.json
+    python tools/make_param_descriptor_fixture.py --novelty [/root/reference] > tests/golden/param_descriptors_novelty.json
 
 Offline clients the reference composes with makeNRTParams (BufMFCC, BufMelBands: rt/MFCCClient.hpp:171-173,
 rt/MelBandsClient.hpp:151-153) get the wrapper's parameters in front exactly as FluidNRTClientWrapper.hpp:33-39, :747-785
@@ -176,6 +177,18 @@ def main_nmfcross():
     sys.stdout.write("\n")
 
 
+def main_novelty():
+    """--novelty: tests/golden/param_descriptors_novelty.json, BufNoveltySlice (slicing wrapper) and BufNoveltyFeature (control wrapper)"""
+    win = wrapper_inputs()
+    out = {}
+    bufs = nrt_buffers("rt/NoveltySliceClient.hpp")
+    out["BufNoveltySlice"] = [bufs[0]] + win + bufs[1:] + table("rt/NoveltySliceClient.hpp")
+    bufs = nrt_buffers("rt/NoveltyFeatureClient.hpp")
+    out["BufNoveltyFeature"] = [bufs[0]] + win + bufs[1:] + [padding_param()] + table("rt/NoveltyFeatureClient.hpp")
+    json.dump(out, sys.stdout, indent=1)
+    sys.stdout.write("\n")
+
+
 def main():
     win = wrapper_inputs()
     pad = padding_param()
@@ -196,5 +209,7 @@ def main():
 if __name__ == "__main__":
     if "--nmfcross" in sys.argv:
         main_nmfcross()
+    elif "--novelty" in sys.argv:
+        main_novelty()
     else:
         main()

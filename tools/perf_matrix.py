@@ -171,6 +171,38 @@ def stft_row(ctx, tm, reps):
             "single_layout": {"ms": ms1, "frames_per_s": B * T / (ms1["min"] * 1e-3), "frac_hbm": nbytes / (ms1["min"] * 1e-3) / 8e12}}
 
 
+def novelty_row(ctx, tm, reps, count, seconds, algorithm, k):
+    """the novelty curve kernel alone on device-resident feature rows at fft 1024 / hop 512 (Spectrum: the magnitudes' padded
+    row stride of 544; MFCC: 13 doubles), next to the STFT launch that produces the magnitudes of the same buffers"""
+    import torch
+    n, win, fft, hop = int(seconds * SR), 1024, 1024, 512
+    T = -(-(-(-(n + hop * (1 + ((k + 1) >> 1) + 1)) // 64) * 64) // hop)      # the slicer's frame count (filter size 1)
+    D, ld = (513, 544) if algorithm == 0 else (13, 13)
+    g = torch.Generator(device="cuda"); g.manual_seed(1)
+    X = torch.rand((count, T, ld), dtype=torch.float64, device="cuda", generator=g)
+    curve = torch.empty((count, T), dtype=torch.float64, device="cuda")
+    dp = ctypes.POINTER(ctypes.c_double)
+
+    def run():
+        rc = ctx.lib.fluhip_novelty_curve_f64(ctx.h, ctypes.cast(X.data_ptr(), dp), count, T, D, ld, k, 1, ctypes.cast(curve.data_ptr(), dp))
+        assert rc == 0
+    torch.cuda.synchronize()
+    run(); ctx.synchronize()
+    ms = stats([tm.time(run) for _ in range(reps)])
+    del X, curve
+    torch.cuda.empty_cache()
+    cor = fluhip.Corpus(ctx, count, n, win, fft, hop, 1)
+    base = np.stack([synth.synth_audio(n, 1000 + b) for b in range(min(count, 16))])
+    cor.set_audio(np.tile(base, (-(-count // len(base)), 1))[:count]); cor.stft_mag_only(); ctx.synchronize()
+    ms_stft = stats([tm.time(cor.stft_mag_only) for _ in range(reps)])
+    cor.close()
+    nbytes = count * T * D * 8.0
+    return {"unit": "ms per novelty-curve call on resident feature rows, device-timed", "ms": ms, "stft_ms": ms_stft,
+            "shape": {"buffers": count, "frames": T, "dims": D, "kernel": k, "plan": ctx.novelty_plan(T, D, k)},
+            "bytes_read": nbytes, "frac_hbm": nbytes / (ms["min"] * 1e-3) / 8e12,
+            "novelty_over_stft": ms["min"] / ms_stft["min"]}
+
+
 def client_row(driver, reps, tmp):
     """the 8-channel x 10 s rank-32 BufNMF job through the C++17 host client (wall time of process(): host timed by necessity
     -- it is a host-side job: gather, upload, 200 iterations, write-back -- min of `reps`)"""
@@ -246,7 +278,7 @@ def main():
         r["wall_s"] = time.perf_counter() - t0
         r["prev"] = PREV.get(n)
         rows[n] = r
-        print(n, json.dumps({k: v for k, v in r.items() if k in ("us", "ms", "error", "ratio_to_equal_length_twin", "sustained_mhz", "single_layout", "batched", "sequential")}),
+        print(n, json.dumps({k: v for k, v in r.items() if k in ("us", "ms", "stft_ms", "frac_hbm", "novelty_over_stft", "error", "ratio_to_equal_length_twin", "sustained_mhz", "single_layout", "batched", "sequential")}),
               file=sys.stderr, flush=True)
 
     put("bench_shard_128x10s_k32", lambda: corpus_row(ctx, 128, 10, 32, 200 // q, R))
@@ -278,6 +310,11 @@ def main():
         print("ragged_256x100", json.dumps({k: rr.get(k) for k in ("us", "ratio_to_equal_length_twin", "error")}), file=sys.stderr, flush=True)
     put("stft_bench_shard", lambda: stft_row(ctx, tm, R))
     put("c5_mfcc_8192x2s", lambda: c5_row(ctx, tm, R))
+    put("novelty_8192x2s_spec_k3", lambda: novelty_row(ctx, tm, R, 8192 // q, 2, 0, 3))
+    put("novelty_8192x2s_spec_k31", lambda: novelty_row(ctx, tm, R, 8192 // q, 2, 0, 31))
+    put("novelty_8192x2s_mfcc_k17", lambda: novelty_row(ctx, tm, R, 8192 // q, 2, 1, 17))
+    put("novelty_1x600s_spec_k31", lambda: novelty_row(ctx, tm, R, 1, 600 // q, 0, 31))
+    put("novelty_1x600s_spec_k101", lambda: novelty_row(ctx, tm, R, 1, 600 // q, 0, 101))   # the tiled form
     put("c3_2x10min_k128_fft4096", lambda: corpus_row(ctx, 2, 600, 128, 40 // min(q, 4), max(3, R - 2), win=4096, fft=4096, hop=1024, tile=441000))
     if want("client_8ch_10s_k32"):
         import importlib.util
