@@ -70,6 +70,8 @@ EXPORTS = [
     "fluhip_nmfcross_process_f64", "fluhip_griffinlim_f64", "fluhip_bufnmfcross_f32", "fluhip_debug_cross_plan", "fluhip_debug_jacobi_svd_f64",
     "fluhip_novelty_curve_f64", "fluhip_novelty_slices_f64", "fluhip_bufnoveltyslice_f32", "fluhip_bufnoveltyfeature_f32",
     "fluhip_debug_novelty_plan",
+    "fluhip_onset_curve_f64", "fluhip_onset_slices_f64", "fluhip_bufonsetslice_f32", "fluhip_bufonsetfeature_f32",
+    "fluhip_debug_onset_plan",
 ]
 
 
@@ -143,6 +145,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.fluhip_bufnoveltyfeature_f32.argtypes = [_vp, _fp, _i64, _i64, ctypes.c_int, _i64, _i64, _i64, _i64, _i64, _dbl,
                                                ctypes.c_int, _fp, _ip]
     L.fluhip_debug_novelty_plan.argtypes = [_vp, _i64, _i64, _i64, _ip]
+    L.fluhip_onset_curve_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, _i64, _i64, _dp, _dp]
+    L.fluhip_onset_slices_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, _i64, _i64, _dbl,
+                                          _i64, _u8p, _ip, _dp]
+    L.fluhip_bufonsetslice_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, ctypes.c_int, _dbl, _i64, _i64, _i64, _i64, _i64,
+                                           _i64, _ip, _i64, _ip]
+    L.fluhip_bufonsetfeature_f32.argtypes = [_vp, _fp, _i64, _i64, ctypes.c_int, _i64, _i64, _i64, _i64, _i64, ctypes.c_int,
+                                             _fp, _ip]
+    L.fluhip_debug_onset_plan.argtypes = [_vp, _i64, _i64, ctypes.c_int, _i64, _ip]
     L.fluhip_corpus_create.argtypes = [_vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
     L.fluhip_corpus_create_ragged.argtypes = [_vp, _i64, _ip, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
     L.fluhip_corpus_frames_of.argtypes = [_vp, _i64]
@@ -608,6 +618,81 @@ class Context:
         self._check(self.lib.fluhip_bufnoveltyfeature_f32(self.h, _f(audio), count, n, algorithm, kernel_size, filter_size,
                                                           w.value, f.value, h.value, sr, padding_mode, _f(out),
                                                           ctypes.byref(Tr)))
+        return out
+
+    # ---- BufOnsetSlice / BufOnsetFeature (util/OnsetDetectionFuncs.hpp, OnsetDetectionFunctions.hpp, OnsetSegmentation.hpp) --
+    @staticmethod
+    def _onset_signal(signal):
+        signal = np.asarray(signal, dtype=np.float64)
+        if signal.ndim == 1:
+            signal = signal[None]
+        assert signal.ndim == 2 and signal.strides[1] == 8
+        count, n = signal.shape
+        ld = signal.strides[0] // 8 if count > 1 else n
+        return signal, count, n, ld
+
+    def onset_curve(self, signal, T, win=1024, fft=1024, hop=512, function=0, filter_size=5, frame_delta=0):
+        """OnsetDetectionFunctions::processFrame over T frames of padded signals [count,n] (or [n]): frame i reads
+        [i hop, i hop + win + d) -> (raw [count,T], filtered [count,T])"""
+        signal, count, n, ld = self._onset_signal(signal)
+        raw = np.empty((count, T))
+        filtered = np.empty((count, T))
+        self._check(self.lib.fluhip_onset_curve_f64(self.h, signal.ctypes.data_as(_dp), count, n, ld, T, win, fft, hop,
+                                                    function, filter_size, frame_delta, _d(raw), _d(filtered)))
+        return raw, filtered
+
+    def onset_slices(self, signal, T, win=1024, fft=1024, hop=512, function=0, filter_size=5, frame_delta=0, threshold=0.5,
+                     min_slice=2):
+        """OnsetSegmentation::processFrame over T frames -> (det [count,T] uint8, counts [count], filtered [count,T])"""
+        signal, count, n, ld = self._onset_signal(signal)
+        filtered = np.empty((count, T))
+        det = np.empty((count, T), dtype=np.uint8)
+        counts = np.empty(count, dtype=np.int64)
+        self._check(self.lib.fluhip_onset_slices_f64(self.h, signal.ctypes.data_as(_dp), count, n, ld, T, win, fft, hop,
+                                                     function, filter_size, frame_delta, threshold, min_slice,
+                                                     det.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)),
+                                                     counts.ctypes.data_as(_ip), _d(filtered)))
+        return det, counts, filtered
+
+    def onset_plan(self, fft, win, function, frame_delta=0):
+        """(form, frames of history recomputed, transforms per frame, frames a workgroup writes); form 0: one fused launch, the
+        spectra stay in the LDS (fft 1024 / 2048 / 4096, even window); form 1: two passes through a workspace (run 0)"""
+        out = (_i64 * 4)()
+        self._check(self.lib.fluhip_debug_onset_plan(self.h, fft, win, function, frame_delta, out))
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    def bufonsetslice(self, audio, function=0, threshold=0.5, min_slice=2, filter_size=5, frame_delta=0, win=1024, fft=-1,
+                      hop=-1, start_frame=0, capacity=None):
+        """NRTOnsetSliceClient on audio [count,channels,n] (or [channels,n] / [n]): a list of int64 index arrays, one per
+        buffer ([-1] when nothing was detected).  capacity: values kept per buffer (default: every possible frame)"""
+        w, h, f = _i64(), _i64(), _i64()
+        self._check(self.lib.fluhip_fft_params(win, hop, fft, ctypes.byref(w), ctypes.byref(h), ctypes.byref(f), None))
+        audio = np.asarray(audio, dtype=np.float32)
+        while audio.ndim < 3:
+            audio = audio[None]
+        audio = np.ascontiguousarray(audio)
+        count, channels, n = audio.shape
+        if capacity is None:
+            capacity = n // h.value + 2
+        idx = np.full((count, max(capacity, 1)), -2, dtype=np.int64)
+        counts = np.zeros(count, dtype=np.int64)
+        self._check(self.lib.fluhip_bufonsetslice_f32(self.h, _f(audio), count, channels, n, start_frame, function, threshold,
+                                                      min_slice, filter_size, frame_delta, w.value, f.value, h.value,
+                                                      idx.ctypes.data_as(_ip), capacity, counts.ctypes.data_as(_ip)))
+        self.last_slice_counts = counts
+        return [idx[b, :min(int(counts[b]), capacity)].copy() for b in range(count)]
+
+    def bufonsetfeature(self, audio, function=0, filter_size=5, frame_delta=0, win=1024, fft=-1, hop=-1, padding_mode=1):
+        """NRTOnsetFeatureClient on mono buffers [count,n] (or [n]) -> float32 [count,frames]"""
+        w, h, f = _i64(), _i64(), _i64()
+        self._check(self.lib.fluhip_fft_params(win, hop, fft, ctypes.byref(w), ctypes.byref(h), ctypes.byref(f), None))
+        audio = np.ascontiguousarray(np.atleast_2d(audio), dtype=np.float32)
+        count, n = audio.shape
+        Tr = _i64(0)
+        args = (function, filter_size, frame_delta, w.value, f.value, h.value, padding_mode)
+        self._check(self.lib.fluhip_bufonsetfeature_f32(self.h, _f(audio), count, n, *args, None, ctypes.byref(Tr)))
+        out = np.empty((count, Tr.value), dtype=np.float32)
+        self._check(self.lib.fluhip_bufonsetfeature_f32(self.h, _f(audio), count, n, *args, _f(out), ctypes.byref(Tr)))
         return out
 
     # ---- profiling ----------------------------------------------------------------------

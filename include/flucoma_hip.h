@@ -34,7 +34,8 @@ extern "C" {
  * fluhip_corpus_last_loop_ms, fluhip_debug_plan_shape, fluhip_debug_wnorm_form.  Nothing of version 4 changed meaning.
  * Added later within 5 (additive only): fluhip_nmfcross_process_f64, fluhip_griffinlim_f64, fluhip_bufnmfcross_f32,
  * fluhip_debug_cross_plan, fluhip_debug_jacobi_svd_f64, fluhip_novelty_curve_f64, fluhip_novelty_slices_f64,
- * fluhip_bufnoveltyslice_f32, fluhip_bufnoveltyfeature_f32, fluhip_debug_novelty_plan. */
+ * fluhip_bufnoveltyslice_f32, fluhip_bufnoveltyfeature_f32, fluhip_debug_novelty_plan, fluhip_onset_curve_f64,
+ * fluhip_onset_slices_f64, fluhip_bufonsetslice_f32, fluhip_bufonsetfeature_f32, fluhip_debug_onset_plan. */
 #define FLUHIP_ABI_VERSION 5
 
 /* clients/common/Result.hpp:24  enum class Status { kOk, kWarning, kError, kCancelled } */
@@ -315,6 +316,68 @@ int fluhip_bufnoveltyfeature_f32(fluhip_ctx* ctx, const float* audio, int64_t co
  * a workgroup holds, curve values it writes}; form 0: band on chip, Gram blocks on the FP64 matrix pipe; 1: band on chip,
  * plain FMAs (D < 32); 2: tiled through a workspace in memory (kernel_size > 65). */
 int fluhip_debug_novelty_plan(fluhip_ctx* ctx, int64_t T, int64_t D, int64_t kernel_size, int64_t* out3);
+
+/* ---- algorithm::OnsetDetectionFunctions / OnsetSegmentation, clients BufOnsetSlice / BufOnsetFeature ---- */
+/* Added within version 5 (additive).  FP64 throughout, every buffer of a call in the same launches.
+ * function (the reference's "metric") 0 Energy, 1 High Frequency Content, 2 Spectral Flux, 3 Modified Kullback-Leibler,
+ * 4 Itakura-Saito, 5 Cosine, 6 Phase Deviation, 7 Weighted Phase Deviation, 8 Complex Domain, 9 Rectified Complex Domain;
+ * filter_size odd in [1, 101]; frame_delta in [0, 8192]; win >= 1, hop >= 1, fft a power of two in [max(4, win), 65536];
+ * threshold >= 0, min_slice >= 0.  Anything else is FLUHIP_ERROR with a message that names the parameter; nothing is
+ * clamped and no output is written.
+ *
+ * The algorithm-level calls take `count` signals of n doubles (stride ld >= n) that the caller has padded already:
+ * frame i reads the samples [i hop, i hop + win + d), d = frame_delta for functions 2, 3, 4 and 0 otherwise (the other
+ * functions ignore frame_delta, as the reference does); samples past n read as zero.  A frame is win samples times a
+ * Hann window, zero-padded at the tail to fft.  With d != 0 the function compares the transform of the samples
+ * [d, d + win) of the slice with that of its first win samples; otherwise the frame with the one or two frames before
+ * it, zero spectra before frame 0.  The "phase" of functions 6 .. 9 is the real part of the complex arctangent of a bin,
+ * as the reference's (util/OnsetDetectionFuncs.hpp:82-128), and wrapPhase is kept as written there.
+ *
+ * OnsetDetectionFunctions::processFrame over T frames (algorithms/public/OnsetDetectionFunctions.hpp:70-114): raw
+ * count x T function values, filtered count x T = raw minus the median of the last filter_size values (zeros before the
+ * start, the value of rank filter_size / 2); below filter_size 3 the reference subtracts a member it never sets and
+ * filtered equals raw.  Either output may be NULL. */
+int fluhip_onset_curve_f64(fluhip_ctx* ctx, const double* signal, int64_t count, int64_t n, int64_t ld, int64_t T, int64_t win,
+                           int64_t fft, int64_t hop, int function, int64_t filter_size, int64_t frame_delta, double* raw,
+                           double* filtered);
+/* OnsetSegmentation::processFrame over T frames (algorithms/public/OnsetSegmentation.hpp:46-66): det count x T bytes, 1
+ * where filtered > threshold with the previous filtered value (0 before frame 0) below it and the debounce counter at
+ * zero; a detection sets the counter to min_slice, every other frame lowers it by one while positive.  counts [count]
+ * detections per signal; filtered (count x T) may be NULL. */
+int fluhip_onset_slices_f64(fluhip_ctx* ctx, const double* signal, int64_t count, int64_t n, int64_t ld, int64_t T, int64_t win,
+                            int64_t fft, int64_t hop, int function, int64_t filter_size, int64_t frame_delta, double threshold,
+                            int64_t min_slice, unsigned char* det, int64_t* counts, double* filtered);
+/* NRTOnsetSliceClient (clients/rt/OnsetSliceClient.hpp behind NRTSliceAdaptor, clients/common/
+ * FluidNRTClientWrapper.hpp:665-725, SpikesToTimes.hpp) for `count` equal-length buffers: audio [count][channels][n]
+ * floats, the channels summed in float.  The derivation: the wrapper appends the client's latency -- one hop
+ * (OnsetSliceClient::latency) -- of zeros and rounds the length up to whole host vectors of 64; BufferedProcess fires a
+ * frame at every multiple i hop below that length, and FluidSource::pull hands it the W = win + d samples that END
+ * there (d = frame_delta for functions 2, 3, 4: OnsetSliceClient::process :89-91), so frame i holds [i hop - W, i hop)
+ * of the sum, zeros outside; the client writes the detection at sample i hop (mFrameOffset).  Detections inside the
+ * first `hop` samples -- frames 0 and 1 -- become ONE at 0, the others are reported as i hop - hop + start_frame while
+ * below n.  For d = 0 this is the framing of the reference's SlicerTestHarness (signal one window in, positions
+ * i hop - hop), whose expected positions the algorithm-level call reproduces.
+ * indices [count][capacity], counts [count] = the TRUE number of values of each buffer (values past `capacity` are
+ * not written); a buffer without detection has count 1 and the single value -1. */
+int fluhip_bufonsetslice_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t channels, int64_t n,
+                             int64_t start_frame, int function, double threshold, int64_t min_slice, int64_t filter_size,
+                             int64_t frame_delta, int64_t win, int64_t fft, int64_t hop, int64_t* indices, int64_t capacity,
+                             int64_t* counts);
+/* NRTOnsetFeatureClient (clients/rt/OnsetFeatureClient.hpp behind StreamingControl, FluidNRTClientWrapper.hpp:551-660)
+ * for `count` equal-length mono buffers: one float per hop (the filtered value), the first latency / hop = 1 value
+ * dropped; padding_mode 0 / 1 / 2 as fluhip_bufnoveltyfeature_f32, computed from win (OnsetFeatureClient::
+ * analysisSettings; the frame delta is not part of it).  Frame j holds the samples [j hop - W - pad, j hop - pad).
+ * out [count][*frames_out] (out == NULL: only *frames_out is set). */
+int fluhip_bufonsetfeature_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int function,
+                               int64_t filter_size, int64_t frame_delta, int64_t win, int64_t fft, int64_t hop,
+                               int padding_mode, float* out, int64_t* frames_out);
+/* Diagnostic: how the onset curve is computed at (fft, win, function, frame_delta) -- nothing else enters: out4 = {form,
+ * frames of history recomputed in front of a run (0, 1 or 2), transforms per frame (2 with a frame delta), frames a
+ * workgroup writes}.  form 0: one fused launch -- a workgroup transforms a run of 32 consecutive frames of one buffer on
+ * chip, keeps their spectra in the LDS and writes one double per frame; built where the project's on-chip FFT core is:
+ * fft 1024, 2048 and 4096 with an even window.  form 1: two passes, the STFT launch writes a round's complex spectra to a
+ * workspace and the reduction reads them (every other shape; run 0). */
+int fluhip_debug_onset_plan(fluhip_ctx* ctx, int64_t fft, int64_t win, int function, int64_t frame_delta, int64_t* out4);
 
 /* ---- feature pipeline: BufMelBands / BufMFCC (BASELINE config 5) ------------------------------ */
 /* Replaces, for `count` equal-length mono buffers at once, the offline-wrapped real-time clients

@@ -16,6 +16,7 @@
 //   rt/MFCCClient.hpp:37-50, :171-173 rt/MelBandsClient.hpp:37-44, :151-153
 //   nrt/NMFCrossClient.hpp:38-48 (tests/golden/param_descriptors_nmfcross.json)
 //   rt/NoveltySliceClient.hpp:44-53, rt/NoveltyFeatureClient.hpp:36-43 (tests/golden/param_descriptors_novelty.json)
+//   rt/OnsetSliceClient.hpp:38-48, rt/OnsetFeatureClient.hpp:29-37 (tests/golden/param_descriptors_onset.json)
 //   rt/NMFFilterClient.hpp:34-38      rt/NMFMatchClient.hpp:32-38       (the two real-time clients behind the offline
 //                                                                        wrapper's parameters, as NMFFilterClient.hpp /
 //                                                                        NMFMatchClient.hpp here describe)
@@ -245,6 +246,42 @@ inline constexpr ParamDescriptor kBufNoveltyFeature[] = {
     enumParam("algorithm", "Algorithm for Feature Extraction", 0, kNoveltyAlgorithms),
     longMin("kernelSize", "KernelSize", 3, 3, "Odd"),
     longMin("filterSize", "Smoothing Filter Size", 1, 1),
+    fft("fftSettings", "FFT Settings", 1024, -1, -1)};
+
+inline constexpr const char* kOnsetMetrics[] = {"Energy", "High Frequency Content", "Spectral Flux", "Modified Kullback-Leibler",
+                                                "Itakura-Saito", "Cosine", "Phase Deviation", "Weighted Phase Deviation",
+                                                "Complex Domain", "Rectified Complex Domain"};
+// LongParam("filterSize", "Filter Size", 5, Min(1), Odd(), Max(101))
+inline constexpr ParamDescriptor kOnsetFilterSize = {"filterSize", "Filter Size", ParamKind::kLong, 5, true, 1, true, 101,
+                                                     nullptr, 0, 0, 0, "Odd"};
+
+// the slicing wrapper's parameters and "indices", then rt/OnsetSliceClient.hpp:38-48
+inline constexpr ParamDescriptor kBufOnsetSlice[] = {
+    inputBuffer("source", "Source Buffer"),
+    longMin("startFrame", "Source Offset", 0, 0),
+    longParam("numFrames", "Number of Frames", -1),
+    longMin("startChan", "Start Channel", 0, 0),
+    longParam("numChans", "Number of Channels", -1),
+    buffer("indices", "Indices Buffer"),
+    enumParam("metric", "Spectral Change Metric", 0, kOnsetMetrics),
+    floatMin("threshold", "Threshold", 0.5, 0),
+    longMin("minSliceLength", "Minimum Length of Slice", 2, 0),
+    kOnsetFilterSize,
+    longMinMax("frameDelta", "Frame Delta", 0, 0, 8192),
+    fft("fftSettings", "FFT Settings", 1024, -1, -1)};
+
+// the control wrapper's parameters, then rt/OnsetFeatureClient.hpp:29-37
+inline constexpr ParamDescriptor kBufOnsetFeature[] = {
+    inputBuffer("source", "Source Buffer"),
+    longMin("startFrame", "Source Offset", 0, 0),
+    longParam("numFrames", "Number of Frames", -1),
+    longMin("startChan", "Start Channel", 0, 0),
+    longParam("numChans", "Number of Channels", -1),
+    buffer("features", "Feature Buffer"),
+    enumParam("padding", "Added Padding", 1, kPaddingModes),
+    enumParam("metric", "Spectral Change Metric", 0, kOnsetMetrics),
+    kOnsetFilterSize,
+    longMinMax("frameDelta", "Frame Delta", 0, 0, 8192),
     fft("fftSettings", "FFT Settings", 1024, -1, -1)};
 
 template <std::size_t N>

@@ -9,6 +9,7 @@ mirrors' tables (include/flucoma_hip/ParamDescriptors.hpp).  tests/test_client.p
     python tools/make_param_descriptor_fixture.py [/root/reference] > tests/golden/param_descriptors.json
     python tools/make_param_descriptor_fixture.py --nmfcross [/root/reference] > tests/golden/param_descriptors_nmfcross.json
     python tools/make_param_descriptor_fixture.py --novelty [/root/reference] > tests/golden/param_descriptors_novelty.json
+    python tools/make_param_descriptor_fixture.py --onset [/root/reference] > tests/golden/param_descriptors_onset.json
 
 Offline clients the reference composes with makeNRTParams (BufMFCC, BufMelBands: rt/MFCCClient.hpp:171-173,
 rt/MelBandsClient.hpp:151-153) get the wrapper's parameters in front exactly as FluidNRTClientWrapper.hpp:33-39, :747-785
@@ -189,6 +190,18 @@ def main_novelty():
     sys.stdout.write("\n")
 
 
+def main_onset():
+    """--onset: tests/golden/param_descriptors_onset.json, BufOnsetSlice (slicing wrapper) and BufOnsetFeature (control wrapper)"""
+    win = wrapper_inputs()
+    out = {}
+    bufs = nrt_buffers("rt/OnsetSliceClient.hpp")
+    out["BufOnsetSlice"] = [bufs[0]] + win + bufs[1:] + table("rt/OnsetSliceClient.hpp")
+    bufs = nrt_buffers("rt/OnsetFeatureClient.hpp")
+    out["BufOnsetFeature"] = [bufs[0]] + win + bufs[1:] + [padding_param()] + table("rt/OnsetFeatureClient.hpp")
+    json.dump(out, sys.stdout, indent=1)
+    sys.stdout.write("\n")
+
+
 def main():
     win = wrapper_inputs()
     pad = padding_param()
@@ -211,5 +224,7 @@ if __name__ == "__main__":
         main_nmfcross()
     elif "--novelty" in sys.argv:
         main_novelty()
+    elif "--onset" in sys.argv:
+        main_onset()
     else:
         main()

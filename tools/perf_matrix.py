@@ -171,6 +171,43 @@ def stft_row(ctx, tm, reps):
             "single_layout": {"ms": ms1, "frames_per_s": B * T / (ms1["min"] * 1e-3), "frac_hbm": nbytes / (ms1["min"] * 1e-3) / 8e12}}
 
 
+def onset_row(ctx, tm, reps, count, seconds, function):
+    """fluhip_onset_curve_f64 at fft 1024 / hop 512 next to the plain STFT launch of the same buffers.  The entry point takes
+    host signals: `ms` is the whole call (host wall time), `upload_ms` a plain copy of the same doubles to the device timed the same
+    way, `device_ms` their difference, `stft_ms` the device-timed STFT of resident float buffers of the same shape"""
+    import torch
+    n, win, fft, hop = int(seconds * SR), 1024, 1024, 512
+    T = (n + win) // hop
+    base = np.stack([synth.synth_audio(n, 2000 + b) for b in range(min(count, 16))]).astype(np.float64)
+    Z = np.zeros((count, n + 2 * win))
+    Z[:, win:win + n] = np.tile(base, (-(-count // len(base)), 1))[:count]
+    raw = np.empty((count, T))
+    dp = ctypes.POINTER(ctypes.c_double)
+
+    def run():
+        rc = ctx.lib.fluhip_onset_curve_f64(ctx.h, Z.ctypes.data_as(dp), count, Z.shape[1], Z.shape[1], T, win, fft, hop, function, 5, 0,
+                                            raw.ctypes.data_as(dp), None)
+        assert rc == 0
+    run(); ctx.synchronize()
+    wall = []
+    for _ in range(reps):
+        t0 = time.perf_counter(); run(); wall.append((time.perf_counter() - t0) * 1e3)
+    ms = stats(wall)
+    up = []
+    for _ in range(reps + 1):
+        t0 = time.perf_counter(); d = torch.from_numpy(Z).cuda(); torch.cuda.synchronize(); up.append((time.perf_counter() - t0) * 1e3); del d
+    upload = stats(up[1:])
+    cor = fluhip.Corpus(ctx, count, n, win, fft, hop, 1)
+    cor.set_audio(np.tile(base.astype(np.float32), (-(-count // len(base)), 1))[:count]); cor.stft_mag_only(); ctx.synchronize()
+    ms_stft = stats([tm.time(cor.stft_mag_only) for _ in range(reps)])
+    cor.close()
+    device_ms = max(ms["min"] - upload["min"], 0.0)
+    return {"unit": "ms per onset-curve call from host signals (host wall time); device_ms = ms - upload_ms", "ms": ms, "upload_ms": upload,
+            "device_ms": device_ms, "stft_ms": ms_stft,
+            "shape": {"buffers": count, "frames": T, "bins": fft // 2 + 1, "function": function, "plan": ctx.onset_plan(fft, win, function)},
+            "onset_over_stft": device_ms / ms_stft["min"]}
+
+
 def novelty_row(ctx, tm, reps, count, seconds, algorithm, k):
     """the novelty curve kernel alone on device-resident feature rows at fft 1024 / hop 512 (Spectrum: the magnitudes' padded
     row stride of 544; MFCC: 13 doubles), next to the STFT launch that produces the magnitudes of the same buffers"""
@@ -278,7 +315,7 @@ def main():
         r["wall_s"] = time.perf_counter() - t0
         r["prev"] = PREV.get(n)
         rows[n] = r
-        print(n, json.dumps({k: v for k, v in r.items() if k in ("us", "ms", "stft_ms", "frac_hbm", "novelty_over_stft", "error", "ratio_to_equal_length_twin", "sustained_mhz", "single_layout", "batched", "sequential")}),
+        print(n, json.dumps({k: v for k, v in r.items() if k in ("us", "ms", "stft_ms", "frac_hbm", "novelty_over_stft", "onset_over_stft", "error", "ratio_to_equal_length_twin", "sustained_mhz", "single_layout", "batched", "sequential")}),
               file=sys.stderr, flush=True)
 
     put("bench_shard_128x10s_k32", lambda: corpus_row(ctx, 128, 10, 32, 200 // q, R))
@@ -315,6 +352,9 @@ def main():
     put("novelty_8192x2s_mfcc_k17", lambda: novelty_row(ctx, tm, R, 8192 // q, 2, 1, 17))
     put("novelty_1x600s_spec_k31", lambda: novelty_row(ctx, tm, R, 1, 600 // q, 0, 31))
     put("novelty_1x600s_spec_k101", lambda: novelty_row(ctx, tm, R, 1, 600 // q, 0, 101))   # the tiled form
+    put("onset_8192x2s_flux", lambda: onset_row(ctx, tm, R, 8192 // q, 2, 2))
+    put("onset_8192x2s_complex", lambda: onset_row(ctx, tm, R, 8192 // q, 2, 8))
+    put("onset_1x600s_rcomplex", lambda: onset_row(ctx, tm, R, 1, 600 // q, 9))
     put("c3_2x10min_k128_fft4096", lambda: corpus_row(ctx, 2, 600, 128, 40 // min(q, 4), max(3, R - 2), win=4096, fft=4096, hop=1024, tile=441000))
     if want("client_8ch_10s_k32"):
         import importlib.util
