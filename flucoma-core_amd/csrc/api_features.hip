@@ -58,6 +58,103 @@ void MelTables::build(bool mfcc, int64_t F, int64_t nBands, int64_t bandsPad, in
   }
 }
 
+// ---- which form a feature call takes (features_common runs by it, fluhip_debug_features_plan reports it) ----------
+static int check_feature_params(fluhip_ctx* ctx, bool mfcc, int64_t fft, int64_t nBands, int64_t nCoefs, int64_t startCoeff,
+                                double minFreq, double maxFreq)
+{
+  if (nBands < 2 || nBands > fft / 2 + 1) return fail(ctx, "numBands must be in [2, fft/2 + 1]");
+  if (!(maxFreq > minFreq)) return fail(ctx, "maxFreq must be above minFreq");
+  if (mfcc && (nCoefs < 2 || nCoefs > nBands || startCoeff < 0 || startCoeff > 1))
+    return fail(ctx, "numCoeffs must be in [2, numBands] and startCoeff in [0, 1]");
+  return FLUHIP_OK;
+}
+
+// fused form (kernels_stft2.hip stft_feat_kernel): the magnitudes never leave the chip.
+// Every bin must lie on the rising edge of at most one band and the falling edge of the band below it, with the
+// bins of each edge contiguous: then band b = (sum of up[f] m[f] over interval b) + (sum of dn[f] m[f] over interval
+// b + 1), interval s = the bins between centres s and s + 1.  True of any filter bank whose triangles are wider than
+// a bin; checked here against the dense matrix, coefficient by coefficient, and anything else takes the two-kernel path.
+// Returns whether the shape runs fused and, if so, leaves the kernel's boundary tables in up / dn / slot.
+static bool fused_features_tables(bool mfcc, int64_t win, int64_t fft, int64_t nBands, int64_t bandsPad, const MelTables& mel,
+                                  std::vector<double>& up, std::vector<double>& dn, std::vector<short>& slot)
+{
+  const int64_t F = fft / 2 + 1, nDct = mel.nDct;
+  const std::vector<double>& filtT = mel.filtT;
+  const int CH = stft_features_bins_per_lane((int) fft);
+  up.assign((size_t) 64 * CH, 0.0);
+  dn.assign((size_t) 64 * CH, 0.0);
+  slot.assign((size_t) 64 * CH, (short) -1);
+  std::vector<int64_t> interval((size_t) F, -1); // interval of bin f, -1: no band touches it
+  // (nDct * nBands <= 4096 bounds the table; the kernel's LDS must also hold its padded rows: stft_features_fits)
+  bool ok = nBands <= 64 && (!mfcc || nDct * nBands <= 4096) && !stft_needs_scratch(win, fft) && (fft == 1024 || fft == 2048) &&
+            (win % 2) == 0 && stft_features_fits((int) fft, (int) nBands, mfcc ? (int) nDct : 0);
+  if (const char* e = fluhip::ab_getenv("FLUHIP_FEAT_FUSED")) // A/B and tests: 0 forces the two-kernel form
+    if (std::atoi(e) == 0) ok = false;
+  std::vector<int64_t> peak((size_t) nBands, 0);
+  for (int64_t b = 0; ok && b < nBands; b++)
+  {
+    double best = -1.0;
+    for (int64_t f = 0; f < F; f++)
+      if (filtT[(size_t) (f * bandsPad + b)] > best) { best = filtT[(size_t) (f * bandsPad + b)]; peak[(size_t) b] = f; }
+    if (best <= 0.0) ok = false; // a band no bin falls into
+  }
+  for (int64_t f = 0; ok && f < F; f++)
+  {
+    int64_t b1 = -1, b2 = -1, cnt = 0;
+    for (int64_t b = 0; b < nBands; b++)
+      if (filtT[(size_t) (f * bandsPad + b)] != 0.0) { if (cnt == 0) b1 = b; else b2 = b; cnt++; }
+    if (cnt == 0) continue;
+    if (cnt > 2 || (cnt == 2 && b2 != b1 + 1)) { ok = false; break; }
+    if (cnt == 2)
+    {
+      interval[(size_t) f] = b2;
+      up[(size_t) f] = filtT[(size_t) (f * bandsPad + b2)];
+      dn[(size_t) f] = filtT[(size_t) (f * bandsPad + b1)];
+    }
+    else if (f <= peak[(size_t) b1]) { interval[(size_t) f] = b1; up[(size_t) f] = filtT[(size_t) (f * bandsPad + b1)]; }
+    else { interval[(size_t) f] = b1 + 1; dn[(size_t) f] = filtT[(size_t) (f * bandsPad + b1)]; }
+  }
+  // interval s starts at bin g[s].  The touched bins must be one contiguous run whose intervals ascend one at a time
+  // from some i0 up to nBands (the falling edge of the last band); intervals below i0 are empty and the running
+  // sums are still 0 at their boundaries, which therefore publish nothing.
+  std::vector<int64_t> g((size_t) nBands + 2, -1);
+  if (ok)
+  {
+    int64_t prev = -1, first = -1, last = -1;
+    bool ended = false;
+    for (int64_t f = 0; f < F && ok; f++)
+    {
+      const int64_t iv = interval[(size_t) f];
+      if (iv < 0) { if (first >= 0) ended = true; continue; }
+      if (ended) { ok = false; break; }              // touched bins are not one contiguous run
+      if (first < 0) first = f;
+      else if (iv != prev && iv != prev + 1) { ok = false; break; }
+      if (iv != prev) g[(size_t) iv] = f;
+      prev = iv;
+      last = f;
+    }
+    if (first < 0 || prev != nBands) ok = false;
+    if (ok)
+    {
+      int64_t i0 = 0;
+      while (g[(size_t) i0] < 0) i0++;
+      for (int64_t sI = 0; sI < i0; sI++) g[(size_t) sI] = first;
+      g[(size_t) nBands + 1] = last + 1;
+      for (int64_t sI = i0 + 1; sI <= nBands + 1; sI++) slot[(size_t) (g[(size_t) sI] - 1)] = (short) sI;
+    }
+    // reconstruction: the segment sums must give back the dense matrix exactly
+    for (int64_t b = 0; ok && b < nBands; b++)
+      for (int64_t f = 0; f < F; f++)
+      {
+        double w = 0.0;
+        if (f >= g[(size_t) b] && f < g[(size_t) b + 1]) w += up[(size_t) f];
+        if (f >= g[(size_t) b + 1] && f < g[(size_t) b + 2]) w += dn[(size_t) f];
+        if (w != filtT[(size_t) (f * bandsPad + b)]) { ok = false; break; }
+      }
+  }
+  return ok;
+}
+
 extern "C" {
 
 // ---- BufSTFT ------------------------------------------------------------------
@@ -172,10 +269,7 @@ static int features_common(fluhip_ctx* ctx, bool mfcc, const float* audio, int64
   if (count < 1) return fail(ctx, "need at least one buffer");
   int rc = check_shape(ctx, n, win, fft, hop, 1);
   if (rc) return rc;
-  if (nBands < 2 || nBands > fft / 2 + 1) return fail(ctx, "numBands must be in [2, fft/2 + 1]");
-  if (!(maxFreq > minFreq)) return fail(ctx, "maxFreq must be above minFreq");
-  if (mfcc && (nCoefs < 2 || nCoefs > nBands || startCoeff < 0 || startCoeff > 1))
-    return fail(ctx, "numCoeffs must be in [2, numBands] and startCoeff in [0, 1]");
+  if ((rc = check_feature_params(ctx, mfcc, fft, nBands, nCoefs, startCoeff, minFreq, maxFreq))) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const int64_t F = fft / 2 + 1;
@@ -195,6 +289,9 @@ static int features_common(fluhip_ctx* ctx, bool mfcc, const float* audio, int64
   if (frames_out) *frames_out = T;
   const int64_t Tp = round_up(T, 32), Fp = round_up(F, 32);
   const int64_t bandsPad = round_up(nBands, 64);
+  // (more than 64 bands never run fused: refused before tables of gigabytes are built for them)
+  if (nBands > 64 && !features_layout(F, bandsPad).fits)
+    return fail(ctx, "too many bands for this fft size: the band energies of a frame do not fit on chip");
   MelTables mel;
   mel.build(mfcc, F, nBands, bandsPad, nCoefs, startCoeff, minFreq, maxFreq, sampleRate);
   const std::vector<double>&filtT = mel.filtT, &wpack = mel.wpack, &dct = mel.dct;
@@ -216,81 +313,10 @@ static int features_common(fluhip_ctx* ctx, bool mfcc, const float* audio, int64
   HIPCHK(ctx, hipMemcpyAsync(dFilt.p, filtT.data(), filtT.size() * sizeof(double), hipMemcpyHostToDevice, s));
   HIPCHK(ctx, hipMemcpyAsync(dDct.p, dct.data(), dct.size() * sizeof(double), hipMemcpyHostToDevice, s));
   // ---- fused form (kernels_stft2.hip stft_feat_kernel): the magnitudes never leave the chip --------------------------
-  // Every bin must lie on the rising edge of at most one band and the falling edge of the band below it, with the
-  // bins of each edge contiguous: then band b = (sum of up[f] m[f] over interval b) + (sum of dn[f] m[f] over interval
-  // b + 1), interval s = the bins between centres s and s + 1.  True of any filter bank whose triangles are wider than
-  // a bin; checked here against the dense matrix, coefficient by coefficient, and anything else takes the two-kernel path.
   {
-    const int CH = stft_features_bins_per_lane((int) fft);
-    std::vector<double> up((size_t) 64 * CH, 0.0), dn((size_t) 64 * CH, 0.0);
-    std::vector<short> slot((size_t) 64 * CH, (short) -1);
-    std::vector<int64_t> interval((size_t) F, -1); // interval of bin f, -1: no band touches it
-    bool ok = nBands <= 64 && (!mfcc || nDct * nBands <= 4096) && !stft_needs_scratch(win, fft) && (fft == 1024 || fft == 2048) &&
-              (win % 2) == 0;
-    if (const char* e = fluhip::ab_getenv("FLUHIP_FEAT_FUSED")) // A/B and tests: 0 forces the two-kernel form
-      if (std::atoi(e) == 0) ok = false;
-    std::vector<int64_t> peak((size_t) nBands, 0);
-    for (int64_t b = 0; ok && b < nBands; b++)
-    {
-      double best = -1.0;
-      for (int64_t f = 0; f < F; f++)
-        if (filtT[(size_t) (f * bandsPad + b)] > best) { best = filtT[(size_t) (f * bandsPad + b)]; peak[(size_t) b] = f; }
-      if (best <= 0.0) ok = false; // a band no bin falls into
-    }
-    for (int64_t f = 0; ok && f < F; f++)
-    {
-      int64_t b1 = -1, b2 = -1, cnt = 0;
-      for (int64_t b = 0; b < nBands; b++)
-        if (filtT[(size_t) (f * bandsPad + b)] != 0.0) { if (cnt == 0) b1 = b; else b2 = b; cnt++; }
-      if (cnt == 0) continue;
-      if (cnt > 2 || (cnt == 2 && b2 != b1 + 1)) { ok = false; break; }
-      if (cnt == 2)
-      {
-        interval[(size_t) f] = b2;
-        up[(size_t) f] = filtT[(size_t) (f * bandsPad + b2)];
-        dn[(size_t) f] = filtT[(size_t) (f * bandsPad + b1)];
-      }
-      else if (f <= peak[(size_t) b1]) { interval[(size_t) f] = b1; up[(size_t) f] = filtT[(size_t) (f * bandsPad + b1)]; }
-      else { interval[(size_t) f] = b1 + 1; dn[(size_t) f] = filtT[(size_t) (f * bandsPad + b1)]; }
-    }
-    // interval s starts at bin g[s].  The touched bins must be one contiguous run whose intervals ascend one at a time
-    // from some i0 up to nBands (the falling edge of the last band); intervals below i0 are empty and the running
-    // sums are still 0 at their boundaries, which therefore publish nothing.
-    std::vector<int64_t> g((size_t) nBands + 2, -1);
-    if (ok)
-    {
-      int64_t prev = -1, first = -1, last = -1;
-      bool ended = false;
-      for (int64_t f = 0; f < F && ok; f++)
-      {
-        const int64_t iv = interval[(size_t) f];
-        if (iv < 0) { if (first >= 0) ended = true; continue; }
-        if (ended) { ok = false; break; }              // touched bins are not one contiguous run
-        if (first < 0) first = f;
-        else if (iv != prev && iv != prev + 1) { ok = false; break; }
-        if (iv != prev) g[(size_t) iv] = f;
-        prev = iv;
-        last = f;
-      }
-      if (first < 0 || prev != nBands) ok = false;
-      if (ok)
-      {
-        int64_t i0 = 0;
-        while (g[(size_t) i0] < 0) i0++;
-        for (int64_t sI = 0; sI < i0; sI++) g[(size_t) sI] = first;
-        g[(size_t) nBands + 1] = last + 1;
-        for (int64_t sI = i0 + 1; sI <= nBands + 1; sI++) slot[(size_t) (g[(size_t) sI] - 1)] = (short) sI;
-      }
-      // reconstruction: the segment sums must give back the dense matrix exactly
-      for (int64_t b = 0; ok && b < nBands; b++)
-        for (int64_t f = 0; f < F; f++)
-        {
-          double w = 0.0;
-          if (f >= g[(size_t) b] && f < g[(size_t) b + 1]) w += up[(size_t) f];
-          if (f >= g[(size_t) b + 1] && f < g[(size_t) b + 2]) w += dn[(size_t) f];
-          if (w != filtT[(size_t) (f * bandsPad + b)]) { ok = false; break; }
-        }
-    }
+    std::vector<double> up, dn;
+    std::vector<short> slot;
+    bool ok = fused_features_tables(mfcc, win, fft, nBands, bandsPad, mel, up, dn, slot);
     if (ok)
     {
       DevBuf dUp, dDn, dSlot, dDct2, dAud, dOutF;
@@ -356,6 +382,8 @@ static int features_common(fluhip_ctx* ctx, bool mfcc, const float* audio, int64
     }
   }
   // ---- two-kernel form: magnitudes through HBM, any filter bank / fft size -------------------------------------------
+  if (!features_layout(F, bandsPad).fits)
+    return fail(ctx, "too many bands for this fft size: the band energies of a frame do not fit on chip");
   // buffers are processed in chunks that keep the magnitude scratch around 2 GiB
   const int64_t perBuf = Tp * Fp * (int64_t) sizeof(double);
   int64_t scratchBytes = 2LL << 30;
@@ -392,13 +420,36 @@ static int features_common(fluhip_ctx* ctx, bool mfcc, const float* audio, int64
     fa.nOut = (int) nOut; fa.out = dOut.as<float>();
     {
       ProfScope p(ctx, 2);
-      launch_features(fa, s);
+      if (!launch_features(fa, s)) return fail(ctx, "internal: the mel kernel has no layout for a shape that was planned");
     }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out + b0 * nOut * T, dOut.p, (size_t) nb * nOut * T * sizeof(float),
                                hipMemcpyDefault, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
   }
+  return FLUHIP_OK;
+}
+
+int fluhip_debug_features_plan(fluhip_ctx* ctx, int mfcc, int64_t win, int64_t fft, int64_t n_bands, int64_t n_coefs,
+                               int64_t start_coeff, double min_freq, double max_freq, double sample_rate, int64_t* out5)
+{
+  if (!out5) return fail(ctx, "null buffer");
+  int rc = check_shape(ctx, 1, win, fft, 1, 1);
+  if (rc) return rc;
+  if ((rc = check_feature_params(ctx, mfcc != 0, fft, n_bands, n_coefs, start_coeff, min_freq, max_freq))) return rc;
+  const int64_t F = fft / 2 + 1, bandsPad = round_up(n_bands, 64);
+  for (int i = 0; i < 5; i++) out5[i] = 0;
+  if (n_bands <= 64) // (the fused form's first condition; the filter bank of thousands of bands is not built to learn that)
+  {
+    MelTables mel;
+    mel.build(mfcc != 0, F, n_bands, bandsPad, n_coefs, start_coeff, min_freq, max_freq, sample_rate);
+    std::vector<double> up, dn;
+    std::vector<short> slot;
+    if (fused_features_tables(mfcc != 0, win, fft, n_bands, bandsPad, mel, up, dn, slot)) return FLUHIP_OK;
+  }
+  const FeatLayout p = features_layout(F, bandsPad);
+  if (!p.fits) return fail(ctx, "too many bands for this fft size: the band energies of a frame do not fit on chip");
+  out5[0] = 1; out5[1] = p.nw; out5[2] = p.ft; out5[3] = (int64_t) p.lds; out5[4] = p.rowsInLds ? 1 : 0;
   return FLUHIP_OK;
 }
 

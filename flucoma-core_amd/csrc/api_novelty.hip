@@ -214,7 +214,7 @@ struct NoveltyFeatures
       fa.magNorm = 0; fa.usePower = 0; fa.logOutput = 1; // processFrame(magnitude, bands, false, false, true) (:157-158)
       fa.dct = dDct.as<double>(); fa.nDct = (int) mel.nDct; fa.startCoeff = 0;
       fa.nOut = (int) kCoefs; fa.out = nullptr; fa.out64 = coef.as<double>();
-      launch_features(fa, s);
+      if (!launch_features(fa, s)) return fail(ctx, "internal: the mel kernel has no layout for the MFCC algorithm's 40 bands");
       *rows = coef.as<double>(); *ldx = kCoefs; *strideX = T * kCoefs;
     }
     HIPCHK(ctx, hipGetLastError());

@@ -365,7 +365,19 @@ struct FeatArgs
   // `out` is not written (the feature rows of the novelty curve)
   double* out64 = nullptr;
 };
-void launch_features(const FeatArgs& a, hipStream_t s);
+// the layout mel_kernel takes for F bins and bandsPad (padded) bands -- a function of the two alone, what launch_features
+// launches and what fluhip_debug_features_plan reports: nw wavefronts per workgroup of ft frames each, the band energies
+// of a frame in the LDS and, with rowsInLds, its magnitude row behind them (otherwise the row is read from memory).
+// fits: lds is within the kFeatLdsLimit bytes the kernel may have; there is no layout for anything else.
+constexpr size_t kFeatLdsLimit = 160 * 1024;
+struct FeatLayout
+{
+  int nw = 4, ft = 4;
+  bool rowsInLds = true, fits = false;
+  size_t lds = 0;
+};
+FeatLayout features_layout(int64_t F, int64_t bandsPad);
+bool launch_features(const FeatArgs& a, hipStream_t s); // false, and nothing launched, when !features_layout(F, bandsPad).fits
 // fused form (kernels_stft2.hip): STFT -> mel bands [-> DCT] without the magnitudes leaving the chip.  up / dn / slot
 // [64 * stft_features_bins_per_lane(fft)]: rising- and falling-edge weight of every bin and the interval boundary a
 // bin closes (or -1); false when the shape has no fused form
@@ -373,6 +385,8 @@ struct StftArgs;
 bool launch_stft_features(const StftArgs& a, const FeatArgs& f, const double* up, const double* dn, const short* slot,
                           hipStream_t s);
 int stft_features_bins_per_lane(int fft);
+// whether the fused kernel is built for this fft size and its LDS holds the DCT rows (nDct 0: mel bands only)
+bool stft_features_fits(int fft, int nBands, int nDct);
 
 // resynthesis: masked inverse STFT of component k with overlap-add
 struct ResynthArgs

@@ -15,11 +15,14 @@
 
 namespace fluhip {
 
-constexpr int kFT = 4; // frames per wavefront (4 x F doubles of LDS each: 16 KB at fft 1024, 64 KB per workgroup)
-
+// kFT: frames per wavefront (4 x F doubles of LDS each: 16 KB at fft 1024, 64 KB per workgroup); 2 or 1 where four rows
+// of a long transform (or of many bands) do not fit beside each other.  ROWS: the magnitude rows are staged in the LDS;
+// without it (a single row of fft 65536 is 256 KB) the gathers read them from memory.  The sums are the same
+// instructions in the same order in every form: a shape computes the same bits whichever layout it is given.
+template <int kFT, bool ROWS>
 __global__ __launch_bounds__(256) void mel_kernel(FeatArgs a)
 {
-  extern __shared__ double lds[]; // [4 waves][kFT][bandsPad] log-band energies for the DCT, then [4 waves][kFT][F] magnitude rows
+  extern __shared__ double lds[]; // [nw waves][kFT][bandsPad] log-band energies for the DCT, then [nw waves][kFT][F] magnitude rows
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = blockIdx.y;
@@ -54,11 +57,14 @@ __global__ __launch_bounds__(256) void mel_kernel(FeatArgs a)
 
   // magnitude rows of this wavefront's frames -> LDS (behind the band scratch)
   double* rows = lds + (size_t) nw * kFT * a.bandsPad + (size_t) wave * kFT * a.F;
-#pragma unroll
-  for (int i = 0; i < kFT; i++)
+  if constexpr (ROWS)
   {
-    const int t = min(t0 + i, a.T - 1);
-    for (int f = lane; f < a.F; f += 64) rows[i * a.F + f] = mag[(int64_t) t * a.ldMag + f];
+#pragma unroll
+    for (int i = 0; i < kFT; i++)
+    {
+      const int t = min(t0 + i, a.T - 1);
+      for (int f = lane; f < a.F; f += 64) rows[i * a.F + f] = mag[(int64_t) t * a.ldMag + f];
+    }
   }
   for (int c0 = 0; c0 < a.nBands; c0 += 64)
   {
@@ -74,7 +80,9 @@ __global__ __launch_bounds__(256) void mel_kernel(FeatArgs a)
 #pragma unroll
       for (int i = 0; i < kFT; i++)
       {
-        double m = rows[i * a.F + f];
+        double m;
+        if constexpr (ROWS) m = rows[i * a.F + f];
+        else m = mag[(int64_t) min(t0 + i, a.T - 1) * a.ldMag + f];
         if (a.magNorm) m = m * scale1;
         if (a.usePower) m = m * m;
         acc[i] += w * m;                                          // :90-91
@@ -140,14 +148,48 @@ __global__ __launch_bounds__(256) void mel_kernel(FeatArgs a)
   }
 }
 
-void launch_features(const FeatArgs& a, hipStream_t s)
+FeatLayout features_layout(int64_t F, int64_t bandsPad)
 {
-  int nw = 4;
-  while (nw > 1 && (size_t) nw * kFT * (a.bandsPad + a.F) * sizeof(double) > 144 * 1024) nw >>= 1;
-  const size_t shmem = (size_t) nw * kFT * (a.bandsPad + a.F) * sizeof(double);
-  request_dynamic_lds(mel_kernel, (size_t) (160 * 1024));
-  dim3 grid((unsigned) ((a.T + nw * kFT - 1) / (nw * kFT)), (unsigned) a.B);
-  hipLaunchKernelGGL(mel_kernel, grid, dim3((unsigned) (64 * nw)), shmem, s, a);
+  FeatLayout p;
+  auto bytes = [&] { return (size_t) p.nw * p.ft * (size_t) (bandsPad + (p.rowsInLds ? F : 0)) * sizeof(double); };
+  // fewer wavefronts first (down to one: fft 8192), then fewer frames per wavefront (fft 16384 and 32768, or thousands of bands)
+  auto shrink = [&] {
+    p.nw = 4; p.ft = 4;
+    while (p.nw > 1 && bytes() > 144 * 1024) p.nw >>= 1;
+    while (p.ft > 1 && bytes() > kFeatLdsLimit) p.ft >>= 1;
+  };
+  shrink();
+  if (bytes() > kFeatLdsLimit) { p.rowsInLds = false; shrink(); } // not one row fits beside the bands (fft 65536): rows from memory
+  p.lds = bytes();
+  p.fits = p.lds <= kFeatLdsLimit;
+  return p;
+}
+
+template <int kFT, bool ROWS>
+static void launch_mel(const FeatArgs& a, const FeatLayout& p, hipStream_t s)
+{
+  request_dynamic_lds(mel_kernel<kFT, ROWS>, kFeatLdsLimit);
+  dim3 grid((unsigned) ((a.T + p.nw * kFT - 1) / (p.nw * kFT)), (unsigned) a.B);
+  hipLaunchKernelGGL((mel_kernel<kFT, ROWS>), grid, dim3((unsigned) (64 * p.nw)), p.lds, s, a);
+}
+
+bool launch_features(const FeatArgs& a, hipStream_t s)
+{
+  const FeatLayout p = features_layout(a.F, a.bandsPad);
+  if (!p.fits) return false;
+  if (p.rowsInLds)
+  {
+    if (p.ft == 4) launch_mel<4, true>(a, p, s);
+    else if (p.ft == 2) launch_mel<2, true>(a, p, s);
+    else launch_mel<1, true>(a, p, s);
+  }
+  else
+  {
+    if (p.ft == 4) launch_mel<4, false>(a, p, s);
+    else if (p.ft == 2) launch_mel<2, false>(a, p, s);
+    else launch_mel<1, false>(a, p, s);
+  }
+  return true;
 }
 
 } // namespace fluhip

@@ -1080,6 +1080,24 @@ __device__ __forceinline__ double wave_shr1(double x) { return dpp_f64<0x138, 0x
 // this shape -- api_features.hip features_common -- and falls back to the two-kernel path otherwise.)
 // No workgroup barrier anywhere in the frame loop: wavefronts are independent.
 // ---------------------------------------------------------------------------------------------------------------
+// alg/MelBands.hpp:95  20 log10(max(eps, band)) of the fused kernels.  The feature leaves as a float: the logarithm is
+// taken in single precision (hardware log2; the band energy rounds to float with 6e-8 relative error = 5e-7 dB, below the
+// float output's own resolution).  A band energy past the float range (float audio within a few orders of FLT_MAX: a band
+// sums hundreds of bins of a window's worth of samples) would round to infinity and the DCT behind it would make NaNs of a
+// whole frame: there, and only there, the exponent is split off first -- frexp, then log2 of the mantissa plus the exponent
+__device__ __forceinline__ float band_db(double v)
+{
+  const float x = (float) fmax(v, kEpsilon);
+  float l = __log2f(x);
+  if (__builtin_expect(x > 3.402823466e38f, 0))
+  {
+    int e;
+    const double m = __builtin_frexp(v, &e);
+    l = __log2f((float) m) + (float) e;
+  }
+  return 6.020599913279624f * l;
+}
+
 struct FeatFusedArgs
 {
   const double* up;    // [64 CH] rising-edge weight of bin f (0 where none)
@@ -1325,7 +1343,7 @@ __global__ __launch_bounds__(64 * NW, SMALL ? 5 : 1) void stft_feat_kernel(StftB
     }
     // :95  20 log10(max(eps, band)).  The feature leaves as a float: the logarithm is taken in single precision (hardware
     // log2; the band energy rounds to float with 6e-8 relative error = 5e-7 dB, below the float output's own resolution)
-    if (fa.logOutput) v = (double) (6.020599913279624f * __log2f((float) fmax(v, kEpsilon)));
+    if (fa.logOutput) v = (double) band_db(v);
     if (!fa.dct)
     {
       if (ln < fa.nBands) fa.out[((int64_t) b * fa.nOut + ln) * a.T + t] = (float) v;
@@ -1510,7 +1528,7 @@ __global__ __launch_bounds__(64 * NW) void stft_feat2_kernel(StftBArgs a, FeatFu
           for (int off = 1; off < 64; off <<= 1) { bs += __shfl_xor(bs, off); e += __shfl_xor(e, off); }
           vv = vv * (e * scale2) / fmax(kEpsilon, bs);
         }
-        if (fa.logOutput) vv = (double) (6.020599913279624f * __log2f((float) fmax(vv, kEpsilon)));
+        if (fa.logOutput) vv = (double) band_db(vv);
         v[f] = vv;
       }
     }
@@ -1591,13 +1609,20 @@ static bool launch_feat2_t(const StftBArgs& k0, const FeatFusedArgs& fa, hipStre
 
 #endif // FLUHIP_AB_SWITCHES
 
+// dynamic LDS of stft_feat_kernel<R1, R2, R3, NW, *, SMALL> with nDct DCT rows over nBands bands (nDct 0: mel bands only)
 template <int R1, int R2, int R3, int NW, bool SMALL = false>
-static bool launch_feat_t(const StftBArgs& k0, const FeatFusedArgs& fa, hipStream_t s)
+static size_t feat_shmem(int nBands, int nDct)
 {
   using Core = FftCore<R1, R2, R3>;
   constexpr int N = Core::N, CH = (N + 1 + 63) / 64, WS = SMALL ? 0 : 2 * (66 + 64) + 64;
-  const size_t shmem = ((size_t) Core::T2 + Core::T3 + (SMALL ? 0 : N) + (R1 == 8 ? N : 0)) * 16 + ((size_t) NW * (Core::BUFD + WS) + 2 * 64 * CH) * 8 +
-                       (fa.dct ? (size_t) fa.nDct * (4 * ((fa.nBands + 3) / 4) + 1) * 8 : 0) + (size_t) 64 * CH * 2 + 16;
+  return ((size_t) Core::T2 + Core::T3 + (SMALL ? 0 : N) + (R1 == 8 ? N : 0)) * 16 + ((size_t) NW * (Core::BUFD + WS) + 2 * 64 * CH) * 8 +
+         (size_t) nDct * (4 * ((nBands + 3) / 4) + 1) * 8 + (size_t) 64 * CH * 2 + 16;
+}
+
+template <int R1, int R2, int R3, int NW, bool SMALL = false>
+static bool launch_feat_t(const StftBArgs& k0, const FeatFusedArgs& fa, hipStream_t s)
+{
+  const size_t shmem = feat_shmem<R1, R2, R3, NW, SMALL>(fa.nBands, fa.dct ? fa.nDct : 0);
   if (shmem > (SMALL ? 80 : 160) * 1024) return false;
   StftBArgs k = k0;
   k.blocksPerBuf = (k.T + NW - 1) / NW;
@@ -1697,6 +1722,13 @@ bool launch_stft_features(const StftArgs& a, const FeatArgs& f, const double* up
   return false;
 }
 int stft_features_bins_per_lane(int fft) { return (fft / 2 + 1 + 63) / 64; }
+bool stft_features_fits(int fft, int nBands, int nDct)
+{
+  // the production forms launch_stft_features picks
+  if (fft == 1024) return feat_shmem<8, 8, 8, 16>(nBands, nDct) <= 160 * 1024;
+  if (fft == 2048) return feat_shmem<16, 8, 8, 8>(nBands, nDct) <= 160 * 1024;
+  return false;
+}
 
 template <int R1, int R2, int R3, int NW, int WINLDS, int FPW = 1, bool DB = false>
 static bool launch_block_t(const StftBArgs& k0, hipStream_t s)

@@ -72,6 +72,7 @@ EXPORTS = [
     "fluhip_debug_novelty_plan",
     "fluhip_onset_curve_f64", "fluhip_onset_slices_f64", "fluhip_bufonsetslice_f32", "fluhip_bufonsetfeature_f32",
     "fluhip_debug_onset_plan",
+    "fluhip_debug_features_plan",
 ]
 
 
@@ -153,6 +154,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.fluhip_bufonsetfeature_f32.argtypes = [_vp, _fp, _i64, _i64, ctypes.c_int, _i64, _i64, _i64, _i64, _i64, ctypes.c_int,
                                              _fp, _ip]
     L.fluhip_debug_onset_plan.argtypes = [_vp, _i64, _i64, ctypes.c_int, _i64, _ip]
+    L.fluhip_debug_features_plan.argtypes = [_vp, ctypes.c_int, _i64, _i64, _i64, _i64, _i64, _dbl, _dbl, _dbl, _ip]
     L.fluhip_corpus_create.argtypes = [_vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
     L.fluhip_corpus_create_ragged.argtypes = [_vp, _i64, _ip, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
     L.fluhip_corpus_frames_of.argtypes = [_vp, _i64]
@@ -440,6 +442,15 @@ class Context:
         self._check(rc)
         assert Tr.value == T
         return out
+
+    def features_plan(self, mfcc, win, fft, n_bands=40, n_coefs=13, start_coeff=0, lo=20.0, hi=20000.0, sr=44100.0):
+        """(form, wavefronts per workgroup, frames per wavefront, dynamic LDS bytes, rows staged) of bufmfcc (mfcc true) /
+        bufmelbands at a shape: form 0 is the fused STFT -> mel -> DCT launch (the other four are 0), form 1 the two-kernel
+        form; rows staged 1: the magnitude rows of a wavefront's frames sit in the LDS, 0: they are read from memory"""
+        out = (_i64 * 5)()
+        self._check(self.lib.fluhip_debug_features_plan(self.h, int(bool(mfcc)), win, fft, n_bands, n_coefs, start_coeff, lo,
+                                                        hi, sr, out))
+        return tuple(int(v) for v in out)
 
     # ---- BufSTFT ----------------------------------------------------------------------------
     def nmfmatch(self, audio, bases, win, fft, hop, seed=42, padding_mode=1):

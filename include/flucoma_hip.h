@@ -35,7 +35,8 @@ extern "C" {
  * Added later within 5 (additive only): fluhip_nmfcross_process_f64, fluhip_griffinlim_f64, fluhip_bufnmfcross_f32,
  * fluhip_debug_cross_plan, fluhip_debug_jacobi_svd_f64, fluhip_novelty_curve_f64, fluhip_novelty_slices_f64,
  * fluhip_bufnoveltyslice_f32, fluhip_bufnoveltyfeature_f32, fluhip_debug_novelty_plan, fluhip_onset_curve_f64,
- * fluhip_onset_slices_f64, fluhip_bufonsetslice_f32, fluhip_bufonsetfeature_f32, fluhip_debug_onset_plan. */
+ * fluhip_onset_slices_f64, fluhip_bufonsetslice_f32, fluhip_bufonsetfeature_f32, fluhip_debug_onset_plan,
+ * fluhip_debug_features_plan. */
 #define FLUHIP_ABI_VERSION 5
 
 /* clients/common/Result.hpp:24  enum class Status { kOk, kWarning, kError, kCancelled } */
@@ -408,6 +409,17 @@ int fluhip_bufmelbands_padded_f32(fluhip_ctx* ctx, const float* audio, int64_t c
 int fluhip_bufmfcc_padded_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win, int64_t fft,
                               int64_t hop, int64_t n_bands, int64_t n_coefs, int64_t start_coeff, double min_freq,
                               double max_freq, double sample_rate, int padding_mode, float* out, int64_t* frames_out);
+/* Diagnostic: the form BufMelBands (mfcc 0) / BufMFCC (mfcc 1) take at a shape -- a function of these parameters only; ctx
+ * receives the message of a refusal and may be NULL.  out5 = {form, wavefronts per workgroup, frames per wavefront, bytes
+ * of dynamic LDS, rows staged}.  form 0: one fused launch, STFT -> mel bands -> DCT with the magnitudes on chip (fft 1024
+ * or 2048, an even window, at most 64 bands, a filter bank whose every bin lies on at most one rising and one falling
+ * edge, and DCT rows that fit the kernel's LDS: at 64 bands 26 rows at fft 1024, 40 at fft 2048); the other four are 0.
+ * form 1: the STFT launch, then the mel kernel over the magnitudes in memory in the layout the other four describe: 4, 2
+ * or 1 wavefronts of 4 frames while that fits 160 KB of LDS, then 2 or 1 frames per wavefront, then (rows staged 0) the
+ * magnitude rows read from memory instead of the LDS.  A band count whose energies alone do not fit (more than 20480
+ * bands) is refused, here as in the calls themselves.  What the tests assert the forms they exercise by. */
+int fluhip_debug_features_plan(fluhip_ctx* ctx, int mfcc, int64_t win, int64_t fft, int64_t n_bands, int64_t n_coefs,
+                               int64_t start_coeff, double min_freq, double max_freq, double sample_rate, int64_t* out5);
 
 /* ---- the users of NMF::processFrame: NMFMatch and NMFFilter ------------------------------------------------------------
  * clients/rt/NMFMatchClient.hpp:76-118 and clients/rt/NMFFilterClient.hpp:69-118 are real-time clients: a host vector in, a
