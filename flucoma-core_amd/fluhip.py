@@ -72,6 +72,7 @@ EXPORTS = [
     "fluhip_debug_novelty_plan",
     "fluhip_onset_curve_f64", "fluhip_onset_slices_f64", "fluhip_bufonsetslice_f32", "fluhip_bufonsetfeature_f32",
     "fluhip_debug_onset_plan",
+    "fluhip_hpss_planes_f64", "fluhip_bufhpss_f32", "fluhip_debug_hpss_plan",
     "fluhip_debug_features_plan",
 ]
 
@@ -154,6 +155,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.fluhip_bufonsetfeature_f32.argtypes = [_vp, _fp, _i64, _i64, ctypes.c_int, _i64, _i64, _i64, _i64, _i64, ctypes.c_int,
                                              _fp, _ip]
     L.fluhip_debug_onset_plan.argtypes = [_vp, _i64, _i64, ctypes.c_int, _i64, _ip]
+    L.fluhip_hpss_planes_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, _dp, _dp, _dp, _dp,
+                                         ctypes.POINTER(_dp)]
+    L.fluhip_bufhpss_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, _dp, _dp, _fp]
+    L.fluhip_debug_hpss_plan.argtypes = [_vp, _i64, _i64, _ip]
     L.fluhip_debug_features_plan.argtypes = [_vp, ctypes.c_int, _i64, _i64, _i64, _i64, _i64, _dbl, _dbl, _dbl, _ip]
     L.fluhip_corpus_create.argtypes = [_vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
     L.fluhip_corpus_create_ragged.argtypes = [_vp, _i64, _ip, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
@@ -705,6 +710,42 @@ class Context:
         out = np.empty((count, Tr.value), dtype=np.float32)
         self._check(self.lib.fluhip_bufonsetfeature_f32(self.h, _f(audio), count, n, *args, _f(out), ctypes.byref(Tr)))
         return out
+
+    # ---- BufHPSS (algorithms/public/HPSS.hpp, clients/rt/HPSSClient.hpp) ----------------------------------------------
+    def hpss_planes(self, mag, h_size=17, v_size=31, mode=0, h_thresh=(0.0, 1.0, 1.0, 1.0), p_thresh=(0.0, 1.0, 1.0, 1.0)):
+        """HPSS::processFrame over magnitude planes [count,T,F] (or [T,F]) -> (hmed, vmed, masks [3]) each [count,T,F]"""
+        mag = np.asarray(mag, dtype=np.float64)
+        if mag.ndim == 2:
+            mag = mag[None]
+        mag = np.ascontiguousarray(mag)
+        count, T, F = mag.shape
+        hmed, vmed = np.empty((count, T, F)), np.empty((count, T, F))
+        masks = np.empty((3, count, T, F))
+        mp = (_dp * 3)(*[_d(masks[i]) for i in range(3)])
+        ht, pt = (ctypes.c_double * 4)(*h_thresh), (ctypes.c_double * 4)(*p_thresh)
+        self._check(self.lib.fluhip_hpss_planes_f64(self.h, _d(mag), count, T, F, F, h_size, v_size, mode, ht, pt, _d(hmed),
+                                                    _d(vmed), mp))
+        return hmed, vmed, masks
+
+    def bufhpss(self, audio, win=1024, fft=-1, hop=-1, h_size=17, v_size=31, mode=0, h_thresh=(0.0, 1.0, 1.0, 1.0),
+                p_thresh=(0.0, 1.0, 1.0, 1.0)):
+        """NRTHPSSClient on mono buffers [count,n] (or [n]) -> float32 [count,3,n]: harmonic, percussive, residual"""
+        w, h, f = _i64(), _i64(), _i64()
+        self._check(self.lib.fluhip_fft_params(win, hop, fft, ctypes.byref(w), ctypes.byref(h), ctypes.byref(f), None))
+        audio = np.ascontiguousarray(np.atleast_2d(audio), dtype=np.float32)
+        count, n = audio.shape
+        out = np.empty((count, 3, n), dtype=np.float32)
+        ht, pt = (ctypes.c_double * 4)(*h_thresh), (ctypes.c_double * 4)(*p_thresh)
+        self._check(self.lib.fluhip_bufhpss_f32(self.h, _f(audio), count, n, w.value, f.value, h.value, h_size, v_size, mode,
+                                                ht, pt, _f(out)))
+        return out
+
+    def hpss_plan(self, h_size, v_size):
+        """(form of the H median, form of the V median, LDS bytes of a workgroup, bins of a workgroup); form 0: the window is
+        ranked from the LDS (sizes up to 63), form 1: from the plane in memory"""
+        out = (_i64 * 4)()
+        self._check(self.lib.fluhip_debug_hpss_plan(self.h, h_size, v_size, out))
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
 
     # ---- profiling ----------------------------------------------------------------------
     def prof_enable(self, on=True):

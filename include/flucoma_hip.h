@@ -36,7 +36,7 @@ extern "C" {
  * fluhip_debug_cross_plan, fluhip_debug_jacobi_svd_f64, fluhip_novelty_curve_f64, fluhip_novelty_slices_f64,
  * fluhip_bufnoveltyslice_f32, fluhip_bufnoveltyfeature_f32, fluhip_debug_novelty_plan, fluhip_onset_curve_f64,
  * fluhip_onset_slices_f64, fluhip_bufonsetslice_f32, fluhip_bufonsetfeature_f32, fluhip_debug_onset_plan,
- * fluhip_debug_features_plan. */
+ * fluhip_debug_features_plan, fluhip_hpss_planes_f64, fluhip_bufhpss_f32, fluhip_debug_hpss_plan. */
 #define FLUHIP_ABI_VERSION 5
 
 /* clients/common/Result.hpp:24  enum class Status { kOk, kWarning, kError, kCancelled } */
@@ -380,6 +380,47 @@ int fluhip_bufonsetfeature_f32(fluhip_ctx* ctx, const float* audio, int64_t coun
  * workspace and the reduction reads them (every other shape; run 0). */
 int fluhip_debug_onset_plan(fluhip_ctx* ctx, int64_t fft, int64_t win, int function, int64_t frame_delta, int64_t* out4);
 
+/* ---- algorithm::HPSS, client BufHPSS (harmonic / percussive separation by median filtering) ---- */
+/* Added within version 5 (additive).  FP64 throughout, every buffer of a call in the same launches.
+ * harm_filter_size and perc_filter_size odd in [3, 1001], perc_filter_size <= bins; mode 0 Classic, 1 Coupled, 2 Advanced;
+ * harm_thresh / perc_thresh: four doubles (x1, y1, x2, y2), frequencies x as fractions of the bins in [0, 1] with x1 <= x2,
+ * amplitudes y in dB (the reference's default is (0, 1, 1, 1); its FrequencyAmpPairConstraint, which clips and swaps, is the
+ * client's).  Anything else is FLUHIP_ERROR with a message that names the parameter; nothing is clamped and no output is
+ * written.
+ *
+ * HPSS::processFrame (algorithms/public/HPSS.hpp:66-152) is a streaming routine with history; over a whole plane whose
+ * row t is the t-th frame it computes, with h2 = (harm_filter_size - 1) / 2 and a median being the value of rank size / 2:
+ *   vmed[t][f]  the median of the bins f .. f + perc_filter_size - 1 of row t, zeros past the last bin (forward-looking);
+ *   hmed[t][f]  the median of bin f over the rows t - h2 - 1 .. t + h2 - 1, zeros outside 0 .. T - 1 (centred ONE ROW BEFORE t);
+ *   mode 0      mult = 1 / max(hmed + vmed, eps): masks hmed mult, vmed mult, 0
+ *   mode 1      harmonic = (hmed / vmed > threshold_h[f]) as 0 / 1, percussive = 1 - harmonic, residual 0
+ *   mode 2      harmonic as in mode 1, percussive = (vmed / hmed > threshold_p[f]), residual = (1 - harmonic)(1 - percussive),
+ *               all three times max(1 / (their sum), eps)
+ * every mask through min(1, .); 0 / 0 compares false, x / 0 true.  threshold[f] is HPSS::makeThreshold (:157-174):
+ * 10^(y1 / 20) below bin floor(x1 bins), 10^(y2 / 20) from bin floor(x2 bins) on, 10^(LinSpaced(y1, y2) / 20) between.
+ * The medians are selections: they are the bits of a sort of the same magnitudes.
+ *
+ * mag count x T x ld doubles (ld >= F); hmed, vmed and the three entries of masks (harmonic, percussive, residual) are
+ * count x T x F each; any of them, and masks itself, may be NULL. */
+int fluhip_hpss_planes_f64(fluhip_ctx* ctx, const double* mag, int64_t count, int64_t T, int64_t F, int64_t ld,
+                           int64_t harm_filter_size, int64_t perc_filter_size, int mode, const double* harm_thresh,
+                           const double* perc_thresh, double* hmed, double* vmed, double* const* masks);
+/* NRTHPSSClient (clients/rt/HPSSClient.hpp behind Streaming, clients/common/FluidNRTClientWrapper.hpp:466-547) for
+ * `count` equal-length mono buffers: audio count x n floats, out count x 3 x n floats (harmonic, percussive, residual; the
+ * residual is always written and is zeros in modes 0 and 1).  The wrapper drops the client's latency
+ * (harm_filter_size - 1) hop + win, which puts every frame back where it came from: frame m = 1, 2, ... covers the samples
+ * [m hop - win, m hop) (Hann window, zero-padded to fft), the planes above are taken over the frames that touch the buffer,
+ * each masked spectrum is transformed back, windowed, overlap-added and divided by the overlap-added window^2.
+ * hop <= win; fft a power of two in [max(4, win), 65536]. */
+int fluhip_bufhpss_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win, int64_t fft, int64_t hop,
+                       int64_t harm_filter_size, int64_t perc_filter_size, int mode, const double* harm_thresh,
+                       const double* perc_thresh, float* out);
+/* Diagnostic: how the masks are computed at (harm_filter_size, perc_filter_size) -- nothing else enters: out4 = {form of
+ * the harmonic median, form of the percussive median, bytes of LDS a workgroup takes, bins a workgroup owns (256)}.  form 0:
+ * the filter's window is copied to the LDS once and ranked from there (sizes up to 63); form 1: ranked straight from the
+ * plane in memory.  ctx may be NULL (no device is used). */
+int fluhip_debug_hpss_plan(fluhip_ctx* ctx, int64_t harm_filter_size, int64_t perc_filter_size, int64_t* out4);
+
 /* ---- feature pipeline: BufMelBands / BufMFCC (BASELINE config 5) ------------------------------ */
 /* Replaces, for `count` equal-length mono buffers at once, the offline-wrapped real-time clients
  *   NRTThreadedMelBandsClient  clients/rt/MelBandsClient.hpp:77-119  (MelBands::processFrame, alg/MelBands.hpp:79-97)
@@ -638,7 +679,8 @@ int  fluhip_balanced_assignment(const double* costs, int64_t n, int world, int32
 /* When enabled, every launch of the two dominant kernel classes is bracketed by hipEvents on
  * the stream it is launched on.  Classes: 0 = the STFT kernel (both magnitude layouts), 1 = nmf_update (both factor
  * updates share one kernel; the split-contraction finalize counts with it), 2 = feature kernels, 3 = the small kernels
- * between the factor updates, 4 = the transposing copy of shapes the block STFT kernel does not cover.  fluhip_prof_read synchronises and returns the launch count and the summed duration
+ * between the factor updates, 4 = the transposing copy of shapes the block STFT kernel does not cover, 5 = the mask kernel of
+ * BufHPSS, 6 = its inverse transforms (one record per round of buffers).  fluhip_prof_read synchronises and returns the launch count and the summed duration
  * since the last reset. */
 int fluhip_prof_enable(fluhip_ctx* ctx, int on);
 int fluhip_prof_reset(fluhip_ctx* ctx);

@@ -17,6 +17,7 @@
 //   nrt/NMFCrossClient.hpp:38-48 (tests/golden/param_descriptors_nmfcross.json)
 //   rt/NoveltySliceClient.hpp:44-53, rt/NoveltyFeatureClient.hpp:36-43 (tests/golden/param_descriptors_novelty.json)
 //   rt/OnsetSliceClient.hpp:38-48, rt/OnsetFeatureClient.hpp:29-37 (tests/golden/param_descriptors_onset.json)
+//   rt/HPSSClient.hpp:37-48, :126-130 (tests/golden/param_descriptors_hpss.json)
 //   rt/NMFFilterClient.hpp:34-38      rt/NMFMatchClient.hpp:32-38       (the two real-time clients behind the offline
 //                                                                        wrapper's parameters, as NMFFilterClient.hpp /
 //                                                                        NMFMatchClient.hpp here describe)
@@ -27,7 +28,7 @@
 
 namespace fluhip {
 
-enum class ParamKind { kInputBuffer, kBuffer, kLong, kFloat, kEnum, kFFT };
+enum class ParamKind { kInputBuffer, kBuffer, kLong, kFloat, kEnum, kFFT, kFloatPairsArray };
 
 struct ParamDescriptor
 {
@@ -43,6 +44,8 @@ struct ParamDescriptor
   int                numEnumStrings;
   long               fftHop, fftSize; // FFT: the other two defaults (-1 = derived: hop = win / 2, fft = nextPow2(win))
   const char*        relational;    // constraints against other parameters, as the reference spells them, or nullptr
+  const double*      pairsDefault;  // FloatPairsArray: the fixedSize default values (x1, y1, x2, y2), else nullptr
+  int                fixedSize;     // FloatPairsArray: 4 (cc/ParameterTypes.hpp:256), else 0
 };
 
 struct ParamDescriptorList
@@ -59,40 +62,46 @@ namespace paramdesc {
 
 constexpr ParamDescriptor inputBuffer(const char* n, const char* d)
 {
-  return {n, d, ParamKind::kInputBuffer, 0, false, 0, false, 0, nullptr, 0, 0, 0, nullptr};
+  return {n, d, ParamKind::kInputBuffer, 0, false, 0, false, 0, nullptr, 0, 0, 0, nullptr, nullptr, 0};
 }
 constexpr ParamDescriptor buffer(const char* n, const char* d)
 {
-  return {n, d, ParamKind::kBuffer, 0, false, 0, false, 0, nullptr, 0, 0, 0, nullptr};
+  return {n, d, ParamKind::kBuffer, 0, false, 0, false, 0, nullptr, 0, 0, 0, nullptr, nullptr, 0};
 }
 constexpr ParamDescriptor longParam(const char* n, const char* d, double def, const char* rel = nullptr)
 {
-  return {n, d, ParamKind::kLong, def, false, 0, false, 0, nullptr, 0, 0, 0, rel};
+  return {n, d, ParamKind::kLong, def, false, 0, false, 0, nullptr, 0, 0, 0, rel, nullptr, 0};
 }
 constexpr ParamDescriptor longMin(const char* n, const char* d, double def, double lo, const char* rel = nullptr)
 {
-  return {n, d, ParamKind::kLong, def, true, lo, false, 0, nullptr, 0, 0, 0, rel};
+  return {n, d, ParamKind::kLong, def, true, lo, false, 0, nullptr, 0, 0, 0, rel, nullptr, 0};
 }
 constexpr ParamDescriptor longMinMax(const char* n, const char* d, double def, double lo, double hi)
 {
-  return {n, d, ParamKind::kLong, def, true, lo, true, hi, nullptr, 0, 0, 0, nullptr};
+  return {n, d, ParamKind::kLong, def, true, lo, true, hi, nullptr, 0, 0, 0, nullptr, nullptr, 0};
 }
 constexpr ParamDescriptor floatMin(const char* n, const char* d, double def, double lo)
 {
-  return {n, d, ParamKind::kFloat, def, true, lo, false, 0, nullptr, 0, 0, 0, nullptr};
+  return {n, d, ParamKind::kFloat, def, true, lo, false, 0, nullptr, 0, 0, 0, nullptr, nullptr, 0};
 }
 constexpr ParamDescriptor floatMinMax(const char* n, const char* d, double def, double lo, double hi)
 {
-  return {n, d, ParamKind::kFloat, def, true, lo, true, hi, nullptr, 0, 0, 0, nullptr};
+  return {n, d, ParamKind::kFloat, def, true, lo, true, hi, nullptr, 0, 0, 0, nullptr, nullptr, 0};
 }
 template <int N>
 constexpr ParamDescriptor enumParam(const char* n, const char* d, double def, const char* const (&s)[N])
 {
-  return {n, d, ParamKind::kEnum, def, true, 0, true, N - 1, s, N, 0, 0, nullptr};
+  return {n, d, ParamKind::kEnum, def, true, 0, true, N - 1, s, N, 0, 0, nullptr, nullptr, 0};
 }
 constexpr ParamDescriptor fft(const char* n, const char* d, long win, long hop, long size)
 {
-  return {n, d, ParamKind::kFFT, static_cast<double>(win), false, 0, false, 0, nullptr, 0, hop, size, nullptr};
+  return {n, d, ParamKind::kFFT, static_cast<double>(win), false, 0, false, 0, nullptr, 0, hop, size, nullptr, nullptr, 0};
+}
+
+// FloatPairsArrayParam: two (frequency, amplitude) pairs, cc/ParameterTypes.hpp:208-258
+constexpr ParamDescriptor floatPairs(const char* n, const char* d, const double (&def)[4], const char* rel)
+{
+  return {n, d, ParamKind::kFloatPairsArray, 0, false, 0, false, 0, nullptr, 0, 0, 0, rel, def, 4};
 }
 
 inline constexpr const char* kUpdateModes[] = {"None", "Seed", "Fixed"};
@@ -253,7 +262,7 @@ inline constexpr const char* kOnsetMetrics[] = {"Energy", "High Frequency Conten
                                                 "Complex Domain", "Rectified Complex Domain"};
 // LongParam("filterSize", "Filter Size", 5, Min(1), Odd(), Max(101))
 inline constexpr ParamDescriptor kOnsetFilterSize = {"filterSize", "Filter Size", ParamKind::kLong, 5, true, 1, true, 101,
-                                                     nullptr, 0, 0, 0, "Odd"};
+                                                     nullptr, 0, 0, 0, "Odd", nullptr, 0};
 
 // the slicing wrapper's parameters and "indices", then rt/OnsetSliceClient.hpp:38-48
 inline constexpr ParamDescriptor kBufOnsetSlice[] = {
@@ -282,6 +291,28 @@ inline constexpr ParamDescriptor kBufOnsetFeature[] = {
     enumParam("metric", "Spectral Change Metric", 0, kOnsetMetrics),
     kOnsetFilterSize,
     longMinMax("frameDelta", "Frame Delta", 0, 0, 8192),
+    fft("fftSettings", "FFT Settings", 1024, -1, -1)};
+
+inline constexpr const char* kHPSSModes[] = {"Classic", "Coupled", "Advanced"};
+inline constexpr double      kHPSSThreshDefault[4] = {0.0, 1.0, 1.0, 1.0}; // FloatPairsArrayT::defaultValue
+
+// the audio wrapper's parameters (cc/FluidNRTClientWrapper.hpp:33-39) and the three output buffers of rt/HPSSClient.hpp:126-130,
+// then rt/HPSSClient.hpp:37-48.  (The two filter sizes are LongParamRuntimeMax<Primary>: their runtime maximum is a host
+// attribute of the real-time object and has no offline meaning.)
+inline constexpr ParamDescriptor kBufHPSS[] = {
+    inputBuffer("source", "Source Buffer"),
+    longMin("startFrame", "Source Offset", 0, 0),
+    longParam("numFrames", "Number of Frames", -1),
+    longMin("startChan", "Start Channel", 0, 0),
+    longParam("numChans", "Number of Channels", -1),
+    buffer("harmonic", "Harmonic Buffer"),
+    buffer("percussive", "Percussive Buffer"),
+    buffer("residual", "Residual Buffer"),
+    longMin("harmFilterSize", "Harmonic Filter Size", 17, 3, "Odd"),
+    longMin("percFilterSize", "Percussive Filter Size", 31, 3, "Odd"),
+    enumParam("maskingMode", "Masking Mode", 0, kHPSSModes),
+    floatPairs("harmThresh", "Harmonic Filter Thresholds", kHPSSThreshDefault, "FrequencyAmpPairConstraint"),
+    floatPairs("percThresh", "Percussive Filter Thresholds", kHPSSThreshDefault, "FrequencyAmpPairConstraint"),
     fft("fftSettings", "FFT Settings", 1024, -1, -1)};
 
 template <std::size_t N>

@@ -10,6 +10,7 @@ mirrors' tables (include/flucoma_hip/ParamDescriptors.hpp).  tests/test_client.p
     python tools/make_param_descriptor_fixture.py --nmfcross [/root/reference] > tests/golden/param_descriptors_nmfcross.json
     python tools/make_param_descriptor_fixture.py --novelty [/root/reference] > tests/golden/param_descriptors_novelty.json
     python tools/make_param_descriptor_fixture.py --onset [/root/reference] > tests/golden/param_descriptors_onset.json
+    python tools/make_param_descriptor_fixture.py --hpss [/root/reference] > tests/golden/param_descriptors_hpss.json
 
 Offline clients the reference composes with makeNRTParams (BufMFCC, BufMelBands: rt/MFCCClient.hpp:171-173,
 rt/MelBandsClient.hpp:151-153) get the wrapper's parameters in front exactly as FluidNRTClientWrapper.hpp:33-39, :747-785
@@ -121,7 +122,7 @@ def parse_entry(entry, index_names, param_names_by_index):
             if mm:
                 d[mm.group(1).lower()] = num(mm.group(2))
                 continue
-            if re.match(r"\w+\(\)$", c):          # a constraint without arguments (Odd())
+            if re.match(r"\w+(\(\)|\{\})$", c):   # a constraint without arguments (Odd() or Odd{})
                 rel.append(c[:-2])
                 continue
             mm = re.match(r"(\w+)<(\w+)>\(\)", c)
@@ -130,9 +131,23 @@ def parse_entry(entry, index_names, param_names_by_index):
             rel.append("%s<%s>" % (mm.group(1), param_names_by_index[index_names.index(mm.group(2))]))
         if rel:
             d["relational"] = ", ".join(rel)
+    elif kind == "FloatPairsArrayParam":
+        d["kind"] = "FloatPairsArray"
+        d["default"], d["fixedSize"] = float_pairs_default()
+        d["relational"] = ", ".join(re.match(r"(\w+)", c).group(1) for c in rest)
     else:
         raise ValueError("parameter kind? " + kind)
     return d
+
+
+def float_pairs_default():
+    """FloatPairsArrayT, clients/common/ParameterTypes.hpp:208-258: (defaultValue's four literals, fixedSize)"""
+    text = strip_comments(open(os.path.join(INC, "common", "ParameterTypes.hpp")).read())
+    body = text[text.index("struct FloatPairsArrayT"):]
+    body = body[:body.index("class FFTParams")]
+    dv = re.search(r"defaultValue\s*\{([^}]*)\}", body).group(1)
+    fs = re.search(r"fixedSize\s*\{\s*(\d+)\s*\}", body).group(1)
+    return [num(t.strip()) for t in dv.split(",")], int(fs)
 
 
 def table(header, which=0):
@@ -202,6 +217,13 @@ def main_onset():
     sys.stdout.write("\n")
 
 
+def main_hpss():
+    """--hpss: tests/golden/param_descriptors_hpss.json, BufHPSS (audio wrapper: source, its offsets, the three output buffers)"""
+    bufs = nrt_buffers("rt/HPSSClient.hpp")
+    json.dump({"BufHPSS": [bufs[0]] + wrapper_inputs() + bufs[1:] + table("rt/HPSSClient.hpp")}, sys.stdout, indent=1)
+    sys.stdout.write("\n")
+
+
 def main():
     win = wrapper_inputs()
     pad = padding_param()
@@ -226,5 +248,7 @@ if __name__ == "__main__":
         main_novelty()
     elif "--onset" in sys.argv:
         main_onset()
+    elif "--hpss" in sys.argv:
+        main_hpss()
     else:
         main()

@@ -240,6 +240,31 @@ def novelty_row(ctx, tm, reps, count, seconds, algorithm, k):
             "novelty_over_stft": ms["min"] / ms_stft["min"]}
 
 
+def hpss_row(ctx, reps, count, seconds, h_size=17, v_size=31, mode=0):
+    """BufHPSS at the client defaults (fft 1024, hop 512) from host buffers, split by the library's own event records
+    (fluhip_prof_read: class 0 the STFT launch, 5 the mask kernel, 6 the inverse transforms of a round), min of `reps`.  The
+    mask kernel's bytes are what it must move: the magnitude plane once, the spectrum once, three spectra out."""
+    n, win, fft, hop = int(seconds * SR), 1024, 1024, 512
+    base = np.stack([synth.synth_audio(n, 1000 + b) for b in range(min(count, 16))]).astype(np.float32)
+    x = np.tile(base, (-(-count // len(base)), 1))[:count]
+    T, F = (n + win + hop - 1) // hop - 1, fft // 2 + 1
+    ctx.bufhpss(x, win, fft, hop, h_size, v_size, mode); ctx.synchronize()      # warm
+    parts = {"stft_ms": [], "mask_ms": [], "inverse_ms": []}
+    ctx.prof_enable(True)
+    for _ in range(reps):
+        ctx.prof_reset()
+        ctx.bufhpss(x, win, fft, hop, h_size, v_size, mode)
+        for key, cls in (("stft_ms", 0), ("mask_ms", 5), ("inverse_ms", 6)):
+            parts[key].append(ctx.prof_read(cls)[1])
+    ctx.prof_enable(False)
+    out = {k: stats(v) for k, v in parts.items()}
+    nbytes = count * T * F * 8.0 * (1 + 2 + 6)
+    return {"unit": "ms per BufHPSS call, device-timed per phase (uploads and the copy back are outside the three figures)", **out,
+            "shape": {"buffers": count, "frames": T, "bins": F, "harmFilterSize": h_size, "percFilterSize": v_size, "mode": mode,
+                      "plan": ctx.hpss_plan(h_size, v_size)},
+            "mask_bytes": nbytes, "mask_frac_hbm": nbytes / (out["mask_ms"]["min"] * 1e-3) / 8e12}
+
+
 def client_row(driver, reps, tmp):
     """the 8-channel x 10 s rank-32 BufNMF job through the C++17 host client (wall time of process(): host timed by necessity
     -- it is a host-side job: gather, upload, 200 iterations, write-back -- min of `reps`)"""
@@ -315,7 +340,7 @@ def main():
         r["wall_s"] = time.perf_counter() - t0
         r["prev"] = PREV.get(n)
         rows[n] = r
-        print(n, json.dumps({k: v for k, v in r.items() if k in ("us", "ms", "stft_ms", "frac_hbm", "novelty_over_stft", "onset_over_stft", "error", "ratio_to_equal_length_twin", "sustained_mhz", "single_layout", "batched", "sequential")}),
+        print(n, json.dumps({k: v for k, v in r.items() if k in ("us", "ms", "stft_ms", "mask_ms", "inverse_ms", "mask_frac_hbm", "frac_hbm", "novelty_over_stft", "onset_over_stft", "error", "ratio_to_equal_length_twin", "sustained_mhz", "single_layout", "batched", "sequential")}),
               file=sys.stderr, flush=True)
 
     put("bench_shard_128x10s_k32", lambda: corpus_row(ctx, 128, 10, 32, 200 // q, R))
@@ -355,6 +380,7 @@ def main():
     put("onset_8192x2s_flux", lambda: onset_row(ctx, tm, R, 8192 // q, 2, 2))
     put("onset_8192x2s_complex", lambda: onset_row(ctx, tm, R, 8192 // q, 2, 8))
     put("onset_1x600s_rcomplex", lambda: onset_row(ctx, tm, R, 1, 600 // q, 9))
+    put("hpss_128x10s_default", lambda: hpss_row(ctx, R, 128 // q, 10))
     put("c3_2x10min_k128_fft4096", lambda: corpus_row(ctx, 2, 600, 128, 40 // min(q, 4), max(3, R - 2), win=4096, fft=4096, hop=1024, tile=441000))
     if want("client_8ch_10s_k32"):
         import importlib.util
