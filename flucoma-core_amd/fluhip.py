@@ -73,6 +73,7 @@ EXPORTS = [
     "fluhip_onset_curve_f64", "fluhip_onset_slices_f64", "fluhip_bufonsetslice_f32", "fluhip_bufonsetfeature_f32",
     "fluhip_debug_onset_plan",
     "fluhip_hpss_planes_f64", "fluhip_bufhpss_f32", "fluhip_debug_hpss_plan",
+    "fluhip_pitch_frames_f64", "fluhip_debug_pitch_curve_f64", "fluhip_bufpitch_f32", "fluhip_debug_pitch_plan",
     "fluhip_debug_features_plan",
 ]
 
@@ -159,6 +160,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                          ctypes.POINTER(_dp)]
     L.fluhip_bufhpss_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, _dp, _dp, _fp]
     L.fluhip_debug_hpss_plan.argtypes = [_vp, _i64, _i64, _ip]
+    L.fluhip_pitch_frames_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, ctypes.c_int, _dbl, _dbl, _dbl, _dp]
+    L.fluhip_debug_pitch_curve_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, ctypes.c_int, _dbl, _dbl, _dbl, _dp]
+    L.fluhip_bufpitch_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _dbl, _dbl,
+                                      ctypes.c_int, ctypes.c_int, _dbl, _fp, _ip]
+    L.fluhip_debug_pitch_plan.argtypes = [_vp, _i64, _i64, ctypes.c_int, _ip]
     L.fluhip_debug_features_plan.argtypes = [_vp, ctypes.c_int, _i64, _i64, _i64, _i64, _i64, _dbl, _dbl, _dbl, _ip]
     L.fluhip_corpus_create.argtypes = [_vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
     L.fluhip_corpus_create_ragged.argtypes = [_vp, _i64, _ip, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
@@ -745,6 +751,54 @@ class Context:
         ranked from the LDS (sizes up to 63), form 1: from the plane in memory"""
         out = (_i64 * 4)()
         self._check(self.lib.fluhip_debug_hpss_plan(self.h, h_size, v_size, out))
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    # ---- BufPitch (algorithms/public/YINFFT.hpp, HPS.hpp, CepstrumF0.hpp, clients/rt/PitchClient.hpp) -------------------
+    def _pitch_mag(self, mag):
+        mag = np.asarray(mag, dtype=np.float64)
+        if mag.ndim == 2:
+            mag = mag[None]
+        return np.ascontiguousarray(mag)
+
+    def pitch_frames(self, mag, algorithm=2, min_freq=20.0, max_freq=10000.0, sample_rate=44100.0):
+        """processFrame of Cepstrum (0), HPS (1) or YinFFT (2) over magnitude planes [count,T,F] (or [T,F]) ->
+        [count,T,2] doubles (pitch in Hz, confidence)"""
+        mag = self._pitch_mag(mag)
+        count, T, F = mag.shape
+        out = np.empty((count, T, 2))
+        self._check(self.lib.fluhip_pitch_frames_f64(self.h, _d(mag), count, T, F, F, algorithm, min_freq, max_freq,
+                                                     sample_rate, _d(out)))
+        return out
+
+    def pitch_curve(self, mag, algorithm=2, min_freq=20.0, max_freq=10000.0, sample_rate=44100.0):
+        """the curve the algorithm searches, [count,T,F]: normalised yin, harmonic product or cepstrum"""
+        mag = self._pitch_mag(mag)
+        count, T, F = mag.shape
+        curve = np.empty((count, T, F))
+        self._check(self.lib.fluhip_debug_pitch_curve_f64(self.h, _d(mag), count, T, F, F, algorithm, min_freq, max_freq,
+                                                          sample_rate, _d(curve)))
+        return curve
+
+    def bufpitch(self, audio, algorithm=2, min_freq=20.0, max_freq=10000.0, unit=0, select=3, win=1024, fft=-1, hop=-1,
+                 padding_mode=1, sample_rate=44100.0):
+        """NRTPitchClient on mono buffers [count,n] (or [n]) -> float32 [count,selected,frames]"""
+        w, h, f = _i64(), _i64(), _i64()
+        self._check(self.lib.fluhip_fft_params(win, hop, fft, ctypes.byref(w), ctypes.byref(h), ctypes.byref(f), None))
+        audio = np.ascontiguousarray(np.atleast_2d(audio), dtype=np.float32)
+        count, n = audio.shape
+        Tr = _i64(0)
+        args = (w.value, f.value, h.value, padding_mode, algorithm, min_freq, max_freq, unit, select, sample_rate)
+        self._check(self.lib.fluhip_bufpitch_f32(self.h, _f(audio), count, n, *args, None, ctypes.byref(Tr)))
+        out = np.empty((count, bin(select & 3).count("1"), Tr.value), dtype=np.float32)
+        self._check(self.lib.fluhip_bufpitch_f32(self.h, _f(audio), count, n, *args, _f(out), ctypes.byref(Tr)))
+        return out
+
+    def pitch_plan(self, fft, win, algorithm):
+        """(form, frames a workgroup of the on-chip form writes, transforms per frame, DCT rows of the cepstrum's GEMM at the
+        default bounds); form 0: transform and pitch in one launch, magnitudes in the LDS (fft 1024 / 2048 / 4096, even
+        window; run 32); form 1: two passes through a magnitude workspace (run 0)"""
+        out = (_i64 * 4)()
+        self._check(self.lib.fluhip_debug_pitch_plan(self.h, fft, win, algorithm, out))
         return int(out[0]), int(out[1]), int(out[2]), int(out[3])
 
     # ---- profiling ----------------------------------------------------------------------

@@ -36,7 +36,8 @@ extern "C" {
  * fluhip_debug_cross_plan, fluhip_debug_jacobi_svd_f64, fluhip_novelty_curve_f64, fluhip_novelty_slices_f64,
  * fluhip_bufnoveltyslice_f32, fluhip_bufnoveltyfeature_f32, fluhip_debug_novelty_plan, fluhip_onset_curve_f64,
  * fluhip_onset_slices_f64, fluhip_bufonsetslice_f32, fluhip_bufonsetfeature_f32, fluhip_debug_onset_plan,
- * fluhip_debug_features_plan, fluhip_hpss_planes_f64, fluhip_bufhpss_f32, fluhip_debug_hpss_plan. */
+ * fluhip_debug_features_plan, fluhip_hpss_planes_f64, fluhip_bufhpss_f32, fluhip_debug_hpss_plan, fluhip_pitch_frames_f64,
+ * fluhip_debug_pitch_curve_f64, fluhip_bufpitch_f32, fluhip_debug_pitch_plan. */
 #define FLUHIP_ABI_VERSION 5
 
 /* clients/common/Result.hpp:24  enum class Status { kOk, kWarning, kError, kCancelled } */
@@ -420,6 +421,38 @@ int fluhip_bufhpss_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64
  * the filter's window is copied to the LDS once and ranked from there (sizes up to 63); form 1: ranked straight from the
  * plane in memory.  ctx may be NULL (no device is used). */
 int fluhip_debug_hpss_plan(fluhip_ctx* ctx, int64_t harm_filter_size, int64_t perc_filter_size, int64_t* out4);
+
+/* ---- BufPitch (clients/rt/PitchClient.hpp: YinFFT, harmonic product spectrum, cepstrum) -------- */
+/* algorithm::CepstrumF0 (0), HPS with nHarmonics = 4 (1) or YINFFT (2) ::processFrame on every frame of `count` magnitude
+ * planes: mag count x T x ld doubles (ld >= F, F = fft / 2 + 1 of a power-of-two fft), out count x T x 2 doubles
+ * (pitch in Hz, confidence).  The reference's behaviour is kept: HPS multiplies mag[j] mag[2 j] mag[3 j] (its loop stops
+ * before nHarmonics), YinFFT clamps its lag range to [min(lrint(sr / max_freq), F - 1), min(lrint(sr / min_freq),
+ * F - minBin - 1)) and takes a frequency of 0 as 1, peaks are the local maxima above the segment's minimum, ordered by
+ * their parabolically interpolated height (equal heights: the lowest index).  Where the reference reads past its arrays
+ * the range is clamped: HPS searches [minBin, min(maxBin, F)), and a quotient sr / freq at or beyond F counts as F before
+ * it is rounded.  Cepstrum needs fft <= 8192 (its DCT table is F x F).  YinFFT takes a squared magnitude at or below
+ * DBL_MIN as zero, here as in fluhip_bufpitch_f32, whose transform returns sqrt(DBL_MIN) for an exactly zero bin (the
+ * reference does not flush; such magnitudes lie 150 orders of magnitude below any sample a float carries). */
+int fluhip_pitch_frames_f64(fluhip_ctx* ctx, const double* mag, int64_t count, int64_t T, int64_t F, int64_t ld, int algorithm,
+                            double min_freq, double max_freq, double sample_rate, double* out);
+/* Diagnostic: the curve the algorithm searches, count x T x F doubles: the normalised yin (NaN in an all-zero frame, as
+ * in the reference), the harmonic product, or the whole cepstrum. */
+int fluhip_debug_pitch_curve_f64(fluhip_ctx* ctx, const double* mag, int64_t count, int64_t T, int64_t F, int64_t ld,
+                                 int algorithm, double min_freq, double max_freq, double sample_rate, double* curve);
+/* NRTPitchClient (PitchClient behind StreamingControl, clients/common/FluidNRTClientWrapper.hpp:551-660) for `count`
+ * equal-length mono buffers: audio count x n floats; padding_mode as in fluhip_bufmfcc_padded_f32; the client's latency
+ * is win.  unit 0: Hz, 1: MIDI (69 + 12 log2(x / 440), -999 for 0).  select: bit 0 pitch, bit 1 confidence; the selected
+ * values are the output channels in that order: out count x selected x frames floats; select 0 is an error.  With out
+ * NULL only *frames_out is written (size query).  sample_rate is the source buffer's. */
+int fluhip_bufpitch_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win, int64_t fft, int64_t hop,
+                        int padding_mode, int algorithm, double min_freq, double max_freq, int unit, int select,
+                        double sample_rate, float* out, int64_t* frames_out);
+/* Diagnostic: how (fft, win, algorithm) is computed: out4 = {form, frames a workgroup of the on-chip form writes,
+ * transforms per frame, rows of the cepstrum's DCT table that are multiplied at the default bounds and 44.1 kHz (0 for the
+ * other algorithms)}.  form 0: transform and pitch in one launch, a run of 32 frames per workgroup, the magnitudes stay in
+ * the LDS -- fft 1024, 2048 and 4096 with an even window.  form 1: the STFT launch leaves a round's magnitudes in a
+ * workspace, the pitch kernels read them (run 0). */
+int fluhip_debug_pitch_plan(fluhip_ctx* ctx, int64_t fft, int64_t win, int algorithm, int64_t* out4);
 
 /* ---- feature pipeline: BufMelBands / BufMFCC (BASELINE config 5) ------------------------------ */
 /* Replaces, for `count` equal-length mono buffers at once, the offline-wrapped real-time clients

@@ -18,6 +18,7 @@
 //   rt/NoveltySliceClient.hpp:44-53, rt/NoveltyFeatureClient.hpp:36-43 (tests/golden/param_descriptors_novelty.json)
 //   rt/OnsetSliceClient.hpp:38-48, rt/OnsetFeatureClient.hpp:29-37 (tests/golden/param_descriptors_onset.json)
 //   rt/HPSSClient.hpp:37-48, :126-130 (tests/golden/param_descriptors_hpss.json)
+//   rt/PitchClient.hpp:39-48, :180-182 (tests/golden/param_descriptors_pitch.json)
 //   rt/NMFFilterClient.hpp:34-38      rt/NMFMatchClient.hpp:32-38       (the two real-time clients behind the offline
 //                                                                        wrapper's parameters, as NMFFilterClient.hpp /
 //                                                                        NMFMatchClient.hpp here describe)
@@ -28,19 +29,19 @@
 
 namespace fluhip {
 
-enum class ParamKind { kInputBuffer, kBuffer, kLong, kFloat, kEnum, kFFT, kFloatPairsArray };
+enum class ParamKind { kInputBuffer, kBuffer, kLong, kFloat, kEnum, kFFT, kFloatPairsArray, kChoices };
 
 struct ParamDescriptor
 {
   const char*        name;
   const char*        displayName;
   ParamKind          kind;
-  double             defaultValue;  // Long / Float / Enum (the index); FFT: the window size
+  double             defaultValue;  // Long / Float / Enum (the index); FFT: the window size; Choices: the bit set (all on)
   bool               hasMin;
   double             min;
   bool               hasMax;
   double             max;
-  const char* const* enumStrings;   // Enum: the choices, else nullptr
+  const char* const* enumStrings;   // Enum, Choices: the strings, else nullptr
   int                numEnumStrings;
   long               fftHop, fftSize; // FFT: the other two defaults (-1 = derived: hop = win / 2, fft = nextPow2(win))
   const char*        relational;    // constraints against other parameters, as the reference spells them, or nullptr
@@ -87,6 +88,16 @@ constexpr ParamDescriptor floatMin(const char* n, const char* d, double def, dou
 constexpr ParamDescriptor floatMinMax(const char* n, const char* d, double def, double lo, double hi)
 {
   return {n, d, ParamKind::kFloat, def, true, lo, true, hi, nullptr, 0, 0, 0, nullptr, nullptr, 0};
+}
+constexpr ParamDescriptor floatMinMaxRel(const char* n, const char* d, double def, double lo, double hi, const char* rel)
+{
+  return {n, d, ParamKind::kFloat, def, true, lo, true, hi, nullptr, 0, 0, 0, rel, nullptr, 0};
+}
+// ChoicesParam: a set of up to 16 named bits, all on by default (cc/ParameterTypes.hpp:134-155)
+template <int N>
+constexpr ParamDescriptor choices(const char* n, const char* d, const char* const (&s)[N])
+{
+  return {n, d, ParamKind::kChoices, static_cast<double>((1 << N) - 1), false, 0, false, 0, s, N, 0, 0, nullptr, nullptr, 0};
 }
 template <int N>
 constexpr ParamDescriptor enumParam(const char* n, const char* d, double def, const char* const (&s)[N])
@@ -313,6 +324,26 @@ inline constexpr ParamDescriptor kBufHPSS[] = {
     enumParam("maskingMode", "Masking Mode", 0, kHPSSModes),
     floatPairs("harmThresh", "Harmonic Filter Thresholds", kHPSSThreshDefault, "FrequencyAmpPairConstraint"),
     floatPairs("percThresh", "Percussive Filter Thresholds", kHPSSThreshDefault, "FrequencyAmpPairConstraint"),
+    fft("fftSettings", "FFT Settings", 1024, -1, -1)};
+
+inline constexpr const char* kPitchSelect[] = {"pitch", "confidence"};
+inline constexpr const char* kPitchAlgorithms[] = {"Cepstrum", "Harmonic Product Spectrum", "YinFFT"};
+inline constexpr const char* kPitchUnits[] = {"Hz", "MIDI"};
+
+// the control wrapper's parameters, then rt/PitchClient.hpp:39-48
+inline constexpr ParamDescriptor kBufPitch[] = {
+    inputBuffer("source", "Source Buffer"),
+    longMin("startFrame", "Source Offset", 0, 0),
+    longParam("numFrames", "Number of Frames", -1),
+    longMin("startChan", "Start Channel", 0, 0),
+    longParam("numChans", "Number of Channels", -1),
+    buffer("features", "Features Buffer"),
+    enumParam("padding", "Added Padding", 1, kPaddingModes),
+    choices("select", "Selection of Outputs", kPitchSelect),
+    enumParam("algorithm", "Algorithm", 2, kPitchAlgorithms),
+    floatMinMaxRel("minFreq", "Low Frequency Bound", 20, 0, 10000, "UpperLimit<maxFreq>"),
+    floatMinMaxRel("maxFreq", "High Frequency Bound", 10000, 1, 20000, "LowerLimit<minFreq>"),
+    enumParam("unit", "Frequency Unit", 0, kPitchUnits),
     fft("fftSettings", "FFT Settings", 1024, -1, -1)};
 
 template <std::size_t N>

@@ -11,6 +11,7 @@ mirrors' tables (include/flucoma_hip/ParamDescriptors.hpp).  tests/test_client.p
     python tools/make_param_descriptor_fixture.py --novelty [/root/reference] > tests/golden/param_descriptors_novelty.json
     python tools/make_param_descriptor_fixture.py --onset [/root/reference] > tests/golden/param_descriptors_onset.json
     python tools/make_param_descriptor_fixture.py --hpss [/root/reference] > tests/golden/param_descriptors_hpss.json
+    python tools/make_param_descriptor_fixture.py --pitch [/root/reference] > tests/golden/param_descriptors_pitch.json
 
 Offline clients the reference composes with makeNRTParams (BufMFCC, BufMelBands: rt/MFCCClient.hpp:171-173,
 rt/MelBandsClient.hpp:151-153) get the wrapper's parameters in front exactly as FluidNRTClientWrapper.hpp:33-39, :747-785
@@ -131,6 +132,10 @@ def parse_entry(entry, index_names, param_names_by_index):
             rel.append("%s<%s>" % (mm.group(1), param_names_by_index[index_names.index(mm.group(2))]))
         if rel:
             d["relational"] = ", ".join(rel)
+    elif kind == "ChoicesParam":
+        d["kind"] = "Choices"
+        d["strings"] = [unquote(r) for r in rest]
+        d["default"] = choices_default(len(rest))
     elif kind == "FloatPairsArrayParam":
         d["kind"] = "FloatPairsArray"
         d["default"], d["fixedSize"] = float_pairs_default()
@@ -148,6 +153,15 @@ def float_pairs_default():
     dv = re.search(r"defaultValue\s*\{([^}]*)\}", body).group(1)
     fs = re.search(r"fixedSize\s*\{\s*(\d+)\s*\}", body).group(1)
     return [num(t.strip()) for t in dv.split(",")], int(fs)
+
+
+def choices_default(n_options):
+    """ChoicesT, clients/common/ParameterTypes.hpp:134-155: defaultValue((1 << numOptions) - 1), every choice on"""
+    text = strip_comments(open(os.path.join(INC, "common", "ParameterTypes.hpp")).read())
+    body = text[text.index("struct ChoicesT"):]
+    if not re.search(r"defaultValue\(\(1 << numOptions\) - 1\)", body[:body.index("};")]):
+        raise ValueError("ChoicesT default?")
+    return (1 << n_options) - 1
 
 
 def table(header, which=0):
@@ -224,6 +238,14 @@ def main_hpss():
     sys.stdout.write("\n")
 
 
+def main_pitch():
+    """--pitch: tests/golden/param_descriptors_pitch.json, BufPitch (control wrapper)"""
+    bufs = nrt_buffers("rt/PitchClient.hpp")
+    json.dump({"BufPitch": [bufs[0]] + wrapper_inputs() + bufs[1:] + [padding_param()] + table("rt/PitchClient.hpp")},
+              sys.stdout, indent=1)
+    sys.stdout.write("\n")
+
+
 def main():
     win = wrapper_inputs()
     pad = padding_param()
@@ -250,5 +272,7 @@ if __name__ == "__main__":
         main_onset()
     elif "--hpss" in sys.argv:
         main_hpss()
+    elif "--pitch" in sys.argv:
+        main_pitch()
     else:
         main()

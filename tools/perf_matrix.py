@@ -265,6 +265,29 @@ def hpss_row(ctx, reps, count, seconds, h_size=17, v_size=31, mode=0):
             "mask_bytes": nbytes, "mask_frac_hbm": nbytes / (out["mask_ms"]["min"] * 1e-3) / 8e12}
 
 
+def pitch_row(ctx, reps, count, seconds, algorithm):
+    """BufPitch at the client defaults (fft 1024, hop 512, 20 .. 10000 Hz) from host buffers: host wall time of the call, min of
+    `reps`, next to the device time of its STFT launch over the same frames (fluhip_prof_read class 0; YinFFT's second
+    transform is outside that record)"""
+    n, win, fft, hop = int(seconds * SR), 1024, 1024, 512
+    base = np.stack([synth.synth_audio(n, 1000 + b) for b in range(min(count, 16))]).astype(np.float32)
+    x = np.tile(base, (-(-count // len(base)), 1))[:count]
+    out = ctx.bufpitch(x, algorithm, win=win, fft=fft, hop=hop); ctx.synchronize()      # warm
+    wall, stft = [], []
+    ctx.prof_enable(True)
+    for _ in range(reps):
+        ctx.prof_reset()
+        t0 = time.perf_counter()
+        ctx.bufpitch(x, algorithm, win=win, fft=fft, hop=hop)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        stft.append(ctx.prof_read(0)[1])
+    ctx.prof_enable(False)
+    return {"unit": "ms per BufPitch call from host buffers (host wall time); stft_ms: its STFT launch, device-timed",
+            "ms": stats(wall), "stft_ms": stats(stft),
+            "shape": {"buffers": count, "frames": int(out.shape[2]), "bins": fft // 2 + 1, "algorithm": algorithm,
+                      "plan": ctx.pitch_plan(fft, win, algorithm)}}
+
+
 def client_row(driver, reps, tmp):
     """the 8-channel x 10 s rank-32 BufNMF job through the C++17 host client (wall time of process(): host timed by necessity
     -- it is a host-side job: gather, upload, 200 iterations, write-back -- min of `reps`)"""
@@ -381,6 +404,9 @@ def main():
     put("onset_8192x2s_complex", lambda: onset_row(ctx, tm, R, 8192 // q, 2, 8))
     put("onset_1x600s_rcomplex", lambda: onset_row(ctx, tm, R, 1, 600 // q, 9))
     put("hpss_128x10s_default", lambda: hpss_row(ctx, R, 128 // q, 10))
+    put("pitch_8192x2s_yin", lambda: pitch_row(ctx, R, 8192 // q, 2, 2))
+    put("pitch_8192x2s_cepstrum", lambda: pitch_row(ctx, R, 8192 // q, 2, 0))
+    put("pitch_1x600s_hps", lambda: pitch_row(ctx, R, 1, 600 // q, 1))
     put("c3_2x10min_k128_fft4096", lambda: corpus_row(ctx, 2, 600, 128, 40 // min(q, 4), max(3, R - 2), win=4096, fft=4096, hop=1024, tile=441000))
     if want("client_8ch_10s_k32"):
         import importlib.util
