@@ -215,6 +215,39 @@ int get_twiddle(fluhip_ctx* ctx, int64_t fft, const double** out)
   return FLUHIP_OK;
 }
 
+int stft_setup(fluhip_ctx* ctx, int64_t win, int64_t fft, int64_t hop, StftSetup* out, int windowType)
+{
+  out->win = win; out->fft = fft; out->hop = hop; out->F = fft / 2 + 1;
+  const int rc = get_window(ctx, win, fft, windowType, &out->window);
+  return rc ? rc : get_twiddle(ctx, fft, &out->twiddle);
+}
+
+int StftSetup::launch(fluhip_ctx* ctx, StftArgs a, int profClass) const
+{
+  a.bigScratch = big_fft_scratch(ctx, win, fft, (int64_t) a.B * a.T);
+  if (stft_needs_scratch(win, fft) && !a.bigScratch) return FLUHIP_ERROR;
+  std::optional<ProfScope> p;
+  if (profClass >= 0) p.emplace(ctx, profClass);
+  launch_stft(a, ctx->stream);
+  return FLUHIP_OK;
+}
+
+int StftSetup::launch(fluhip_ctx* ctx, ResynthArgs r) const
+{
+  r.bigScratch = big_fft_scratch(ctx, win, fft, r.T);
+  if (stft_needs_scratch(win, fft) && !r.bigScratch) return FLUHIP_ERROR;
+  launch_resynth(r, ctx->stream);
+  return FLUHIP_OK;
+}
+
+int check_fft_settings(fluhip_ctx* ctx, int64_t win, int64_t fft, int64_t hop)
+{
+  if (win < 1 || hop < 1) return fail(ctx, "fftSettings: window and hop sizes must be positive");
+  if (fft < 4 || (fft & (fft - 1)) || fft < win || !stft_supported(win, fft))
+    return fail(ctx, "fftSettings: fft size must be a power of two >= window size, from 4 to 65536");
+  return FLUHIP_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // C ABI: context, parameter arithmetic, profiling aid
 // ---------------------------------------------------------------------------------------

@@ -735,21 +735,14 @@ int corpus_stft(fluhip_corpus* c, const float* a32, const double* a64, int64_t a
   // magOnly: the frame-major magnitudes alone (what STFT::process + STFT::magnitude compute, alg/STFT.hpp:90-108, 61-66);
   // the bin-major copy is written for the factor updates only -- half the kernel's store traffic
   fluhip_ctx* ctx = c->ctx;
-  const double *wtab = nullptr, *ttab = nullptr;
-  int rc = get_window(ctx, c->win, c->fft, c->windowType, &wtab);
-  if (rc) return rc;
-  rc = get_twiddle(ctx, c->fft, &ttab);
+  StftSetup st;
+  const int rc = stft_setup(ctx, c->win, c->fft, c->hop, &st, c->windowType);
   if (rc) return rc;
   if (c->keepSpec && !c->spec.p)
     HIPCHK(ctx, c->spec.alloc((size_t) c->B * c->T * c->F * 2 * sizeof(double), false, ctx->stream));
-  StftArgs a;
-  a.audio = a32; a.audio64 = a64; a.n = c->n; a.audioStride = audioStride;
-  a.win = (int) c->win; a.fft = (int) c->fft; a.hop = (int) c->hop;
-  a.T = (int) c->T; a.F = (int) c->F; a.B = (int) c->B;
-  a.window = wtab; a.twiddle = ttab;
+  StftArgs a = st.args(a32, a64, c->n, audioStride, c->B, c->T, -(c->win / 2)); // STFT::process
   a.mag = c->mag.as<double>(); a.magStride = c->Tp * c->Fp; a.ldMag = c->Fp;
   a.spec = c->keepSpec ? c->spec.as<double>() : nullptr; a.specStride = c->T * c->F * 2;
-  a.frameOffset = 0;
   a.nTab = c->ragged ? c->nTab.as<int64_t>() : nullptr;
   a.bigScratch = big_fft_scratch(ctx, c->win, c->fft, c->B * c->T);
   if (stft_needs_scratch(c->win, c->fft) && !a.bigScratch) return FLUHIP_ERROR;
@@ -1448,7 +1441,8 @@ int corpus_iterate(fluhip_corpus* c, int64_t iters, bool updateW, bool updateH,
 // C ABI
 // Host allocations inside the library (std::vector images of seeds, plans, staging) can throw: nothing may cross the C ABI.
 // std::bad_alloc is classified like a device out-of-memory (fluhip_last_error_is_out_of_memory), anything else is an error.
-template <typename Fn> static int guarded(fluhip_ctx* ctx, Fn&& fn)
+// (The corpus entry points keep this guard of their own: its texts differ from api_internal.h's `guarded`.)
+template <typename Fn> static int guarded_corpus(fluhip_ctx* ctx, Fn&& fn)
 {
   try { return fn(); }
   catch (const std::bad_alloc&) { return fail_oom(ctx, "out of host memory inside libflucoma_hip"); }
@@ -2061,48 +2055,48 @@ int fluhip_corpus_update_clocks(fluhip_corpus* c, int64_t* out8, int reset)
 int fluhip_corpus_create(fluhip_ctx* ctx, int64_t count, int64_t n, int64_t win, int64_t fft,
                          int64_t hop, int64_t K, fluhip_corpus** out)
 {
-  return guarded(ctx, [&] { return fluhip_corpus_create_impl(ctx, count, n, win, fft, hop, K, out); });
+  return guarded_corpus(ctx, [&] { return fluhip_corpus_create_impl(ctx, count, n, win, fft, hop, K, out); });
 }
 
 int fluhip_corpus_set_audio_host(fluhip_corpus* c, const float* audio)
 {
-  return guarded((c ? c->ctx : nullptr), [&] { return fluhip_corpus_set_audio_host_impl(c, audio); });
+  return guarded_corpus((c ? c->ctx : nullptr), [&] { return fluhip_corpus_set_audio_host_impl(c, audio); });
 }
 
 int fluhip_corpus_stft(fluhip_corpus* c)
 {
-  return guarded((c ? c->ctx : nullptr), [&] { return fluhip_corpus_stft_impl(c); });
+  return guarded_corpus((c ? c->ctx : nullptr), [&] { return fluhip_corpus_stft_impl(c); });
 }
 
 int fluhip_corpus_set_factors(fluhip_corpus* c, const float* bases_seed, const float* acts_seed)
 {
-  return guarded((c ? c->ctx : nullptr), [&] { return fluhip_corpus_set_factors_impl(c, bases_seed, acts_seed); });
+  return guarded_corpus((c ? c->ctx : nullptr), [&] { return fluhip_corpus_set_factors_impl(c, bases_seed, acts_seed); });
 }
 
 int fluhip_corpus_nmf(fluhip_corpus* c, int64_t iters, int update_w, int update_h, int64_t seed,
                       const int64_t* seeds, fluhip_progress_fn progress, void* user)
 {
-  return guarded((c ? c->ctx : nullptr), [&] { return fluhip_corpus_nmf_impl(c, iters, update_w, update_h, seed, seeds, progress, user); });
+  return guarded_corpus((c ? c->ctx : nullptr), [&] { return fluhip_corpus_nmf_impl(c, iters, update_w, update_h, seed, seeds, progress, user); });
 }
 
 int fluhip_corpus_writeback_host(fluhip_corpus* c, float* bases, float* acts)
 {
-  return guarded((c ? c->ctx : nullptr), [&] { return fluhip_corpus_writeback_host_impl(c, bases, acts); });
+  return guarded_corpus((c ? c->ctx : nullptr), [&] { return fluhip_corpus_writeback_host_impl(c, bases, acts); });
 }
 
 int fluhip_corpus_resynth_host(fluhip_corpus* c, float* out)
 {
-  return guarded((c ? c->ctx : nullptr), [&] { return fluhip_corpus_resynth_host_impl(c, out); });
+  return guarded_corpus((c ? c->ctx : nullptr), [&] { return fluhip_corpus_resynth_host_impl(c, out); });
 }
 
 int fluhip_corpus_resynth_interleaved_host(fluhip_corpus* c, float* out, int64_t frame_stride)
 {
-  return guarded((c ? c->ctx : nullptr), [&] { return fluhip_corpus_resynth_interleaved_host_impl(c, out, frame_stride); });
+  return guarded_corpus((c ? c->ctx : nullptr), [&] { return fluhip_corpus_resynth_interleaved_host_impl(c, out, frame_stride); });
 }
 
 int fluhip_corpus_keep_spectrum(fluhip_corpus* c, int on)
 {
-  return guarded((c ? c->ctx : nullptr), [&] { return fluhip_corpus_keep_spectrum_impl(c, on); });
+  return guarded_corpus((c ? c->ctx : nullptr), [&] { return fluhip_corpus_keep_spectrum_impl(c, on); });
 }
 
 } // extern "C"

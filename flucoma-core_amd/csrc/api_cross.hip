@@ -6,34 +6,7 @@
 #include "api_internal.h"
 #include "fluhip_cross.h"
 
-#include <new>
-
 namespace {
-
-// std::bad_alloc on the host is an out-of-memory failure like a device allocation
-template <typename Fn> int guarded_cross(fluhip_ctx* ctx, Fn&& fn)
-{
-  if (!ctx) return FLUHIP_ERROR;
-  try
-  {
-    return fn();
-  }
-  catch (const std::bad_alloc&)
-  {
-    return fail_oom(ctx, "host allocation failed");
-  }
-  catch (...)
-  {
-    return fail(ctx, "internal error");
-  }
-}
-
-#define ALLOC(ctx, buf, bytes, zero)                                                                  \
-  do                                                                                                  \
-  {                                                                                                   \
-    hipError_t e__ = (buf).alloc((bytes), (zero), (ctx)->stream);                                     \
-    if (e__ != hipSuccess) return fail_hip((ctx), e__, "device allocation of the NMFCross workspace"); \
-  } while (0)
 
 // The H-update loop of NMFCross::multiplicativeUpdates (:156-186) on device data: X [T][F] (ld F), W [K][F] (ld F,
 // clamped to eps in place), H [T][ldh] out (ldh = K).  progress(1..iters) with the context's run-ahead bound.
@@ -53,8 +26,8 @@ int cross_loop(const CrossLoop& L, fluhip_progress_fn progress, void* user)
   hipStream_t s = ctx->stream;
   const int64_t T = L.T, F = L.F, K = L.K, ldh = K;
   DevBuf dsum, denergy, Hc, Hs, Q, part;
-  ALLOC(ctx, dsum, (size_t) K * sizeof(double), false);
-  ALLOC(ctx, denergy, (size_t) K * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", dsum, (size_t) K * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", denergy, (size_t) K * sizeof(double), false);
   launch_cross_dict(L.W, F, (int) K, (int) F, dsum.as<double>(), denergy.as<double>(), s);
   // H = EigenRandom<MatrixXd>(K, T, seed, [0, 1)) (:70-71): column-major K x T, one draw per value -- entry (k, t) is draw
   // t K + k, which is H1[t][k] of the T x K layout here
@@ -66,10 +39,10 @@ int cross_loop(const CrossLoop& L, fluhip_progress_fn progress, void* user)
   }
   const int cus = std::max(1, ctx->props.multiProcessorCount);
   const CrossGemmPlan p1 = cross_gemm_plan(T, F, K, cus), p2 = cross_gemm_plan(T, K, F, cus);
-  ALLOC(ctx, Hc, (size_t) (T * ldh) * sizeof(double), false);
-  ALLOC(ctx, Hs, (size_t) (T * ldh) * sizeof(double), false);
-  ALLOC(ctx, Q, (size_t) (T * F) * sizeof(double), false);
-  ALLOC(ctx, part, (size_t) std::max<int64_t>(std::max(p1.partDoubles, p2.partDoubles), 1) * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", Hc, (size_t) (T * ldh) * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", Hs, (size_t) (T * ldh) * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", Q, (size_t) (T * F) * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", part, (size_t) std::max<int64_t>(std::max(p1.partDoubles, p2.partDoubles), 1) * sizeof(double), false);
   double* H = L.Hout;
   // measurement builds only (fluhip_env.h): FLUHIP_CROSS_WIDE=1 runs the same H update on the any-rank path of the plain NMF
   // (kernels_nmf_wide.hip: dgemm_tile_kernel, the ratio and apply launches) -- the A/B baseline of tools/nmfcross_bench.py
@@ -79,10 +52,10 @@ int cross_loop(const CrossLoop& L, fluhip_progress_fn progress, void* user)
   DevBuf WT, XT, HW, wideScr;
   if (wide)
   {
-    ALLOC(ctx, WT, (size_t) (round_up(F, 32) * Kp) * sizeof(double), true);
-    ALLOC(ctx, XT, (size_t) (F * T) * sizeof(double), false);
-    ALLOC(ctx, HW, (size_t) (round_up(T, 32) * Kp) * sizeof(double), true);
-    ALLOC(ctx, wideScr, (size_t) nmf_update_wide_scratch_doubles((int) F, (int) T, (int) Kp, 1) * sizeof(double), false);
+    DEV_ALLOC(ctx, "NMFCross", WT, (size_t) (round_up(F, 32) * Kp) * sizeof(double), true);
+    DEV_ALLOC(ctx, "NMFCross", XT, (size_t) (F * T) * sizeof(double), false);
+    DEV_ALLOC(ctx, "NMFCross", HW, (size_t) (round_up(T, 32) * Kp) * sizeof(double), true);
+    DEV_ALLOC(ctx, "NMFCross", wideScr, (size_t) nmf_update_wide_scratch_doubles((int) F, (int) T, (int) Kp, 1) * sizeof(double), false);
     launch_transpose(L.W, F, 0, WT.as<double>(), Kp, 0, (int) K, (int) F, 1, s);
     launch_transpose(L.X, F, 0, XT.as<double>(), T, 0, (int) T, (int) F, 1, s);
   }
@@ -164,19 +137,17 @@ int griffinlim_dev(fluhip_ctx* ctx, double* spec, int64_t T, int64_t F, int64_t 
                    int64_t fft, int64_t hop, int64_t seed)
 {
   hipStream_t s = ctx->stream;
-  const double *wtab = nullptr, *ttab = nullptr;
-  int rc = get_window(ctx, win, fft, FLUHIP_WINDOW_HANN, &wtab);
-  if (rc) return rc;
-  rc = get_twiddle(ctx, fft, &ttab);
+  StftSetup st;
+  int rc = stft_setup(ctx, win, fft, hop, &st);
   if (rc) return rc;
   const int64_t n = T * F;
   DevBuf mag, phase, est, prev, tmp, frames;
-  ALLOC(ctx, mag, (size_t) n * sizeof(double), false);
-  ALLOC(ctx, phase, (size_t) n * 2 * sizeof(double), false);
-  ALLOC(ctx, est, (size_t) n * 2 * sizeof(double), true);  // estimate = 0 (:39)
-  ALLOC(ctx, prev, (size_t) n * 2 * sizeof(double), true);
-  ALLOC(ctx, tmp, (size_t) nSamples * sizeof(double), false);
-  ALLOC(ctx, frames, (size_t) (T * win) * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", mag, (size_t) n * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", phase, (size_t) n * 2 * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", est, (size_t) n * 2 * sizeof(double), true);  // estimate = 0 (:39)
+  DEV_ALLOC(ctx, "NMFCross", prev, (size_t) n * 2 * sizeof(double), true);
+  DEV_ALLOC(ctx, "NMFCross", tmp, (size_t) nSamples * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", frames, (size_t) (T * win) * sizeof(double), false);
   // magnitude = |in| (:37)
   launch_mag_hypot(spec, (int) T, (int) F, mag.as<double>(), F, s);
   // phase = EigenRandomPhase<ArrayXXcd>(T, F, seed) (:38, util/EigenRandom.hpp:147-160): column-major, entry (t, f) is draw
@@ -196,26 +167,18 @@ int griffinlim_dev(fluhip_ctx* ctx, double* spec, int64_t T, int64_t F, int64_t 
     launch_gl_apply(mag.as<double>(), phase.as<double>(), spec, n, s);
     HIPCHK(ctx, hipStreamSynchronize(s));
   }
-  ResynthArgs ra;
-  ra.spec = spec; ra.Wf = nullptr; ra.H1 = nullptr; ra.Vhat = nullptr; ra.ldV = 0; ra.Kp = 0; ra.k = 0;
-  ra.win = (int) win; ra.fft = (int) fft; ra.hop = (int) hop; ra.T = (int) T; ra.F = (int) F;
-  ra.window = wtab; ra.twiddle = ttab; ra.frames = frames.as<double>(); ra.out = tmp.as<double>(); ra.out32 = nullptr;
-  ra.n = nSamples; ra.trim = win / 2;
-  ra.bigScratch = big_fft_scratch(ctx, win, fft, T);
-  if (stft_needs_scratch(win, fft) && !ra.bigScratch) return FLUHIP_ERROR;
-  StftArgs sa;
-  sa.audio = nullptr; sa.audio64 = tmp.as<double>(); sa.n = nSamples; sa.audioStride = nSamples;
-  sa.win = (int) win; sa.fft = (int) fft; sa.hop = (int) hop; sa.T = (int) T; sa.F = (int) F; sa.B = 1;
-  sa.window = wtab; sa.twiddle = ttab; sa.mag = nullptr; sa.magStride = 0; sa.ldMag = 0;
-  sa.specStride = n * 2; sa.frameOffset = 0; sa.bigScratch = ra.bigScratch;
+  ResynthArgs ra = st.resynth(spec, T, frames.as<double>(), nSamples, win / 2); // ISTFT::process
+  ra.out = tmp.as<double>();
+  StftArgs sa = st.args(nullptr, tmp.as<double>(), nSamples, nSamples, 1, T, -(win / 2)); // STFT::process
+  sa.specStride = n * 2;
   double* e = est.as<double>();
   double* pv = prev.as<double>();
   for (int64_t i = 0; i < iters; i++)
   {
     std::swap(e, pv);                 // prev = estimate (:41)
-    launch_resynth(ra, s);            // istft(magnitude * phase) (:42-43)
+    if ((rc = st.launch(ctx, ra))) return rc; // istft(magnitude * phase) (:42-43)
     sa.spec = e;
-    launch_stft(sa, s);               // estimate = stft(tmp) (:44)
+    if ((rc = st.launch(ctx, sa))) return rc; // estimate = stft(tmp) (:44)
     launch_gl_update(mag.as<double>(), e, pv, spec, n, s); // phase update (:45-46); spec = magnitude * phase
     HIPCHK(ctx, hipGetLastError());
   }
@@ -236,9 +199,9 @@ int nmfcross_process_impl(fluhip_ctx* ctx, const double* X, int64_t T, int64_t F
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   DevBuf dX, dW, dH;
-  ALLOC(ctx, dX, (size_t) (T * F) * sizeof(double), false);
-  ALLOC(ctx, dW, (size_t) (K * F) * sizeof(double), false);
-  ALLOC(ctx, dH, (size_t) (T * K) * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", dX, (size_t) (T * F) * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", dW, (size_t) (K * F) * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", dH, (size_t) (T * K) * sizeof(double), false);
   HIPCHK(ctx, hipMemcpy2DAsync(dX.p, (size_t) F * sizeof(double), X, (size_t) ldx * sizeof(double), (size_t) F * sizeof(double),
                                (size_t) T, hipMemcpyHostToDevice, s));
   HIPCHK(ctx, hipMemcpy2DAsync(dW.p, (size_t) F * sizeof(double), W0, (size_t) ldw * sizeof(double), (size_t) F * sizeof(double),
@@ -266,7 +229,7 @@ int griffinlim_impl(fluhip_ctx* ctx, double* spec, int64_t T, int64_t F, int64_t
   hipStream_t s = ctx->stream;
   DevBuf d;
   const size_t nb = (size_t) (T * F) * 2 * sizeof(double);
-  ALLOC(ctx, d, nb, false);
+  DEV_ALLOC(ctx, "NMFCross", d, nb, false);
   HIPCHK(ctx, hipMemcpyAsync(d.p, spec, nb, hipMemcpyHostToDevice, s));
   if ((rc = griffinlim_dev(ctx, d.as<double>(), T, F, nSamples, iters, win, fft, hop, seed))) return rc;
   if ((rc = copy_to_host(ctx, spec, nb, d.p, nb, nb, 1, s))) return rc;
@@ -280,24 +243,17 @@ int cross_stft(fluhip_ctx* ctx, const float* audio, int64_t n, int64_t stride, i
 {
   hipStream_t s = ctx->stream;
   const int64_t T = (n + hop) / hop, F = fft / 2 + 1;
-  const double *wtab = nullptr, *ttab = nullptr;
-  int rc = get_window(ctx, win, fft, FLUHIP_WINDOW_HANN, &wtab);
-  if (rc) return rc;
-  rc = get_twiddle(ctx, fft, &ttab);
+  StftSetup st;
+  int rc = stft_setup(ctx, win, fft, hop, &st);
   if (rc) return rc;
   DevBuf in;
-  ALLOC(ctx, in, (size_t) n * sizeof(float), false);
+  DEV_ALLOC(ctx, "NMFCross", in, (size_t) n * sizeof(float), false);
   HIPCHK(ctx, upload_strided(in.p, audio, (size_t) n, (size_t) stride, sizeof(float), s));
-  ALLOC(ctx, spec, (size_t) (T * F) * 2 * sizeof(double), false);
-  ALLOC(ctx, mag, (size_t) (T * F) * sizeof(double), false);
-  StftArgs a;
-  a.audio = in.as<float>(); a.audio64 = nullptr; a.n = n; a.audioStride = n;
-  a.win = (int) win; a.fft = (int) fft; a.hop = (int) hop; a.T = (int) T; a.F = (int) F; a.B = 1;
-  a.window = wtab; a.twiddle = ttab; a.mag = nullptr; a.magStride = 0; a.ldMag = 0;
-  a.spec = spec.as<double>(); a.specStride = T * F * 2; a.frameOffset = 0;
-  a.bigScratch = big_fft_scratch(ctx, win, fft, T);
-  if (stft_needs_scratch(win, fft) && !a.bigScratch) return FLUHIP_ERROR;
-  launch_stft(a, s);
+  DEV_ALLOC(ctx, "NMFCross", spec, (size_t) (T * F) * 2 * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", mag, (size_t) (T * F) * sizeof(double), false);
+  StftArgs a = st.args(in.as<float>(), nullptr, n, n, 1, T, -(win / 2));
+  a.spec = spec.as<double>(); a.specStride = T * F * 2;
+  if ((rc = st.launch(ctx, a))) return rc;
   launch_mag_hypot(spec.as<double>(), (int) T, (int) F, mag.as<double>(), F, s);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(s)); // (`in` is released behind the launches)
@@ -330,7 +286,7 @@ int bufnmfcross_impl(fluhip_ctx* ctx, const float* source, int64_t nSrc, int64_t
   if ((rc = cross_stft(ctx, source, nSrc, srcStride, win, fft, hop, srcSpec, srcMag))) return rc;
   if ((rc = cross_stft(ctx, target, nTgt, tgtStride, win, fft, hop, tgtSpec, tgtMag))) return rc;
   tgtSpec.release();
-  ALLOC(ctx, H, (size_t) (T * K) * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", H, (size_t) (T * K) * sizeof(double), false);
   // nmf.process(tgtMag, outputEnvelopes, W, r, min(srcWindows, p), c, seed) (:157-159)
   CrossLoop L{ctx, tgtMag.as<double>(), srcMag.as<double>(), T, F, K, r, std::min(srcWindows, p), c, iters, seed, H.as<double>()};
   if ((rc = cross_loop(L, progress, user))) return rc;
@@ -343,12 +299,12 @@ int bufnmfcross_impl(fluhip_ctx* ctx, const float* source, int64_t nSrc, int64_t
   };
   // NMFCross::synthesize (:49-57): result [T][2F] = H1 [T][K] . srcSpectrum [K][2F] -- one real GEMM over the interleaved
   // complex matrix
-  ALLOC(ctx, result, (size_t) (T * F) * 2 * sizeof(double), false);
+  DEV_ALLOC(ctx, "NMFCross", result, (size_t) (T * F) * 2 * sizeof(double), false);
   {
     const int cus = std::max(1, ctx->props.multiProcessorCount);
     const CrossGemmPlan ps = cross_gemm_plan(T, 2 * F, K, cus);
     DevBuf part;
-    ALLOC(ctx, part, (size_t) std::max<int64_t>(ps.partDoubles, 1) * sizeof(double), false);
+    DEV_ALLOC(ctx, "NMFCross", part, (size_t) std::max<int64_t>(ps.partDoubles, 1) * sizeof(double), false);
     CrossGemm g;
     g.A = H.as<double>(); g.lda = K; g.B = srcSpec.as<double>(); g.ldb = 2 * F; g.C = result.as<double>(); g.ldc = 2 * F;
     g.M = T; g.N = 2 * F; g.Kd = K;
@@ -363,20 +319,14 @@ int bufnmfcross_impl(fluhip_ctx* ctx, const float* source, int64_t nSrc, int64_t
   if ((rc = step(iters + 2))) return rc;
   // istft.process(result, resultAudio) (:175): tgtFrames samples, to float
   {
-    const double *wtab = nullptr, *ttab = nullptr;
-    if ((rc = get_window(ctx, win, fft, FLUHIP_WINDOW_HANN, &wtab))) return rc;
-    if ((rc = get_twiddle(ctx, fft, &ttab))) return rc;
+    StftSetup st;
+    if ((rc = stft_setup(ctx, win, fft, hop, &st))) return rc;
     DevBuf frames;
-    ALLOC(ctx, frames, (size_t) (T * win) * sizeof(double), false);
-    ALLOC(ctx, dout, (size_t) nTgt * sizeof(float), false);
-    ResynthArgs ra;
-    ra.spec = result.as<double>(); ra.Wf = nullptr; ra.H1 = nullptr; ra.Vhat = nullptr; ra.ldV = 0; ra.Kp = 0; ra.k = 0;
-    ra.win = (int) win; ra.fft = (int) fft; ra.hop = (int) hop; ra.T = (int) T; ra.F = (int) F;
-    ra.window = wtab; ra.twiddle = ttab; ra.frames = frames.as<double>(); ra.out = nullptr; ra.out32 = dout.as<float>();
-    ra.n = nTgt; ra.trim = win / 2;
-    ra.bigScratch = big_fft_scratch(ctx, win, fft, T);
-    if (stft_needs_scratch(win, fft) && !ra.bigScratch) return FLUHIP_ERROR;
-    launch_resynth(ra, s);
+    DEV_ALLOC(ctx, "NMFCross", frames, (size_t) (T * win) * sizeof(double), false);
+    DEV_ALLOC(ctx, "NMFCross", dout, (size_t) nTgt * sizeof(float), false);
+    ResynthArgs ra = st.resynth(result.as<double>(), T, frames.as<double>(), nTgt, win / 2);
+    ra.out32 = dout.as<float>();
+    if ((rc = st.launch(ctx, ra))) return rc;
     HIPCHK(ctx, hipGetLastError());
     if ((rc = step(iters + 3))) return rc;
   }
@@ -404,7 +354,7 @@ int fluhip_nmfcross_process_f64(fluhip_ctx* ctx, const double* X, int64_t T, int
                                 int64_t K, int64_t ldw, int64_t time_sparsity, int64_t polyphony, int64_t continuity,
                                 int64_t iters, int64_t seed, double* H1, fluhip_progress_fn progress, void* user)
 {
-  return guarded_cross(ctx, [&] {
+  return guarded(ctx, [&] {
     return nmfcross_process_impl(ctx, X, T, F, ldx, W0, K, ldw, time_sparsity, polyphony, continuity, iters, seed, H1,
                                  progress, user);
   });
@@ -413,7 +363,7 @@ int fluhip_nmfcross_process_f64(fluhip_ctx* ctx, const double* X, int64_t T, int
 int fluhip_griffinlim_f64(fluhip_ctx* ctx, double* spec, int64_t T, int64_t F, int64_t n_samples, int64_t iters,
                           int64_t win, int64_t fft, int64_t hop, int64_t seed)
 {
-  return guarded_cross(ctx, [&] { return griffinlim_impl(ctx, spec, T, F, n_samples, iters, win, fft, hop, seed); });
+  return guarded(ctx, [&] { return griffinlim_impl(ctx, spec, T, F, n_samples, iters, win, fft, hop, seed); });
 }
 
 int fluhip_bufnmfcross_f32(fluhip_ctx* ctx, const float* source, int64_t n_src, int64_t src_stride, const float* target,
@@ -421,7 +371,7 @@ int fluhip_bufnmfcross_f32(fluhip_ctx* ctx, const float* source, int64_t n_src, 
                            int64_t time_sparsity, int64_t polyphony, int64_t continuity, int64_t iters, int64_t seed,
                            float* out, fluhip_progress_fn progress, void* user)
 {
-  return guarded_cross(ctx, [&] {
+  return guarded(ctx, [&] {
     return bufnmfcross_impl(ctx, source, n_src, src_stride, target, n_tgt, tgt_stride, win, fft, hop, time_sparsity,
                             polyphony, continuity, iters, seed, out, progress, user);
   });

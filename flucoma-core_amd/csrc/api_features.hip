@@ -155,19 +155,10 @@ static bool fused_features_tables(bool mfcc, int64_t win, int64_t fft, int64_t n
   return ok;
 }
 
-extern "C" {
-
 // ---- BufSTFT ------------------------------------------------------------------
-static int64_t bufstft_padding(int64_t win, int64_t hop, int mode)
+static int bufstft_forward(fluhip_ctx* ctx, const float* audio, int64_t n, int64_t stride, int64_t win, int64_t fft, int64_t hop,
+                           int padding_mode, float* mag, float* phase, int64_t* hops_out)
 {
-  return mode == 0 ? 0 : (mode == 1 ? win >> 1 : win - hop); // cc/ParameterTypes.hpp:315-323
-}
-
-int fluhip_bufstft_forward_f32(fluhip_ctx* ctx, const float* audio, int64_t n, int64_t stride, int64_t win,
-                               int64_t fft, int64_t hop, int padding_mode, float* mag, float* phase,
-                               int64_t* hops_out)
-{
-  if (!ctx) return FLUHIP_ERROR;
   if (!audio) return fail(ctx, "No input buffer supplied");
   if (!mag && !phase) return fail(ctx, "Neither magnitude nor phase buffer supplied");
   if (padding_mode < 0 || padding_mode > 2) return fail(ctx, "padding mode must be 0, 1 or 2");
@@ -178,32 +169,21 @@ int fluhip_bufstft_forward_f32(fluhip_ctx* ctx, const float* audio, int64_t n, i
     return fail(ctx, "Can produce up to 65536 channels. Split your data up and try again");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const int64_t F = fft / 2 + 1, pad = bufstft_padding(win, hop, padding_mode);
-  int64_t padded = n + 2 * pad;                                      // :121-124
-  if (padding_mode == 2) padded = ((padded + hop - 1) / hop) * hop;   // :125-127
-  if (padded < win) return fail(ctx, "not enough frames");
-  const int64_t T = 1 + (padded - win) / hop;                         // :129-130
+  const ControlFrames g = control_frames(n, win, hop, padding_mode, 0); // :121-130: no latency, every frame kept
+  const int64_t F = fft / 2 + 1, T = g.T;
+  if (g.paddedLength < win) return fail(ctx, "not enough frames");
   if (hops_out) *hops_out = T;
-  const double *wtab = nullptr, *ttab = nullptr;
-  rc = get_window(ctx, win, fft, FLUHIP_WINDOW_HANN, &wtab);
-  if (rc) return rc;
-  rc = get_twiddle(ctx, fft, &ttab);
-  if (rc) return rc;
+  StftSetup st;
+  if ((rc = stft_setup(ctx, win, fft, hop, &st))) return rc;
   DevBuf in, spec, dm, dp;
   HIPCHK(ctx, in.alloc((size_t) n * sizeof(float), false, s));
   HIPCHK(ctx, upload_strided(in.p, audio, (size_t) n, (size_t) stride, sizeof(float), s));
   HIPCHK(ctx, spec.alloc((size_t) T * F * 2 * sizeof(double), false, s));
   if (mag) HIPCHK(ctx, dm.alloc((size_t) T * F * sizeof(float), false, s));
   if (phase) HIPCHK(ctx, dp.alloc((size_t) T * F * sizeof(float), false, s));
-  StftArgs sa;
-  sa.audio = in.as<float>(); sa.audio64 = nullptr; sa.n = n; sa.audioStride = n;
-  sa.win = (int) win; sa.fft = (int) fft; sa.hop = (int) hop; sa.T = (int) T; sa.F = (int) F; sa.B = 1;
-  sa.window = wtab; sa.twiddle = ttab; sa.mag = nullptr; sa.magStride = 0; sa.ldMag = 0;
-  sa.spec = spec.as<double>(); sa.specStride = 0;
-  sa.frameOffset = (int) (win / 2 - pad); // frame i starts at sample i*hop - padding (:151-162)
-  sa.bigScratch = big_fft_scratch(ctx, win, fft, T);
-  if (stft_needs_scratch(win, fft) && !sa.bigScratch) return FLUHIP_ERROR;
-  launch_stft(sa, s);
+  StftArgs sa = st.args(in.as<float>(), nullptr, n, n, 1, T, -g.userPad); // frame i starts at sample i*hop - padding (:151-162)
+  sa.spec = spec.as<double>();
+  if ((rc = st.launch(ctx, sa))) return rc;
   launch_spec_to_magphase(spec.as<double>(), (int) T, (int) F, mag ? dm.as<float>() : nullptr,
                           phase ? dp.as<float>() : nullptr, s);
   HIPCHK(ctx, hipGetLastError());
@@ -213,10 +193,9 @@ int fluhip_bufstft_forward_f32(fluhip_ctx* ctx, const float* audio, int64_t n, i
   return FLUHIP_OK;
 }
 
-int fluhip_bufstft_inverse_f32(fluhip_ctx* ctx, const float* mag, const float* phase, int64_t hops, int64_t win,
-                               int64_t fft, int64_t hop, int padding_mode, float* out, int64_t* n_out)
+static int bufstft_inverse(fluhip_ctx* ctx, const float* mag, const float* phase, int64_t hops, int64_t win, int64_t fft,
+                           int64_t hop, int padding_mode, float* out, int64_t* n_out)
 {
-  if (!ctx) return FLUHIP_ERROR;
   if (!mag || !phase) return fail(ctx, "Need both magnutude and phase buffers for inverse transform");
   if (padding_mode < 0 || padding_mode > 2) return fail(ctx, "padding mode must be 0, 1 or 2");
   if (hops < 1) return fail(ctx, "not enough frames");
@@ -224,16 +203,13 @@ int fluhip_bufstft_inverse_f32(fluhip_ctx* ctx, const float* mag, const float* p
   if (rc) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const int64_t F = fft / 2 + 1, T = hops, pad = bufstft_padding(win, hop, padding_mode);
+  const int64_t F = fft / 2 + 1, T = hops, pad = user_padding(win, hop, padding_mode);
   const int64_t paddedOut = (T - 1) * hop + win; // nrt/BufSTFTClient.hpp:233
   const int64_t finalOut = paddedOut - pad;      // :234
   if (n_out) *n_out = finalOut;
   if (!out) return FLUHIP_OK;                    // size query
-  const double *wtab = nullptr, *ttab = nullptr;
-  rc = get_window(ctx, win, fft, FLUHIP_WINDOW_HANN, &wtab);
-  if (rc) return rc;
-  rc = get_twiddle(ctx, fft, &ttab);
-  if (rc) return rc;
+  StftSetup st;
+  if ((rc = stft_setup(ctx, win, fft, hop, &st))) return rc;
   DevBuf dm, dp, spec, frames, dout;
   HIPCHK(ctx, dm.alloc((size_t) T * F * sizeof(float), false, s));
   HIPCHK(ctx, dp.alloc((size_t) T * F * sizeof(float), false, s));
@@ -243,14 +219,9 @@ int fluhip_bufstft_inverse_f32(fluhip_ctx* ctx, const float* mag, const float* p
   HIPCHK(ctx, hipMemcpyAsync(dm.p, mag, (size_t) T * F * sizeof(float), hipMemcpyHostToDevice, s));
   HIPCHK(ctx, hipMemcpyAsync(dp.p, phase, (size_t) T * F * sizeof(float), hipMemcpyHostToDevice, s));
   launch_polar_to_spec(dm.as<float>(), dp.as<float>(), (int) T, (int) F, spec.as<double>(), s);
-  ResynthArgs ra;
-  ra.spec = spec.as<double>(); ra.Wf = nullptr; ra.H1 = nullptr; ra.Vhat = nullptr; ra.ldV = 0; ra.Kp = 0; ra.k = 0;
-  ra.win = (int) win; ra.fft = (int) fft; ra.hop = (int) hop; ra.T = (int) T; ra.F = (int) F;
-  ra.window = wtab; ra.twiddle = ttab; ra.frames = frames.as<double>(); ra.out = nullptr;
-  ra.out32 = dout.as<float>(); ra.n = finalOut; ra.trim = pad;
-  ra.bigScratch = big_fft_scratch(ctx, ra.win, ra.fft, ra.T);
-  if (stft_needs_scratch(ra.win, ra.fft) && !ra.bigScratch) return FLUHIP_ERROR;
-  launch_resynth(ra, s);
+  ResynthArgs ra = st.resynth(spec.as<double>(), T, frames.as<double>(), finalOut, pad);
+  ra.out32 = dout.as<float>();
+  if ((rc = st.launch(ctx, ra))) return rc;
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(out, dout.p, (size_t) finalOut * sizeof(float), hipMemcpyDeviceToHost, s));
   HIPCHK(ctx, hipStreamSynchronize(s));
@@ -263,7 +234,6 @@ static int features_common(fluhip_ctx* ctx, bool mfcc, const float* audio, int64
                            double minFreq, double maxFreq, double sampleRate, int normalize, int scaleDb,
                            int paddingMode, float* out, int64_t* frames_out)
 {
-  if (!ctx) return FLUHIP_ERROR;
   if (!audio || !out) return fail(ctx, "null buffer");
   if (paddingMode < 0 || paddingMode > 2) return fail(ctx, "padding mode must be 0 (None), 1 (Default) or 2 (Full)");
   if (count < 1) return fail(ctx, "need at least one buffer");
@@ -273,18 +243,10 @@ static int features_common(fluhip_ctx* ctx, bool mfcc, const float* audio, int64
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const int64_t F = fft / 2 + 1;
-  // StreamingControl bookkeeping (cc/FluidNRTClientWrapper.hpp:564-579, 642-644)
-  // userPadding.first = FFTParams::padding (cc/ParameterTypes.hpp:315-323): 0 / win/2 / win - hop; the input sits that
-  // far into the padded signal, the client's latency (= win) is added in front of the analysis, the padded length is
-  // rounded up to whole hops in Full mode (:572-574), and the first latency / hop output frames are dropped (:643-656)
-  const int64_t latencyHops = win / hop;
-  const int64_t userPad = paddingMode == 0 ? 0 : paddingMode == 1 ? win / 2 : win - hop;
-  int64_t paddedLength = n + win + 2 * userPad;
-  if (paddingMode == 2) paddedLength = ((paddedLength + hop - 1) / hop) * hop;
-  const int64_t T = 1 + (paddedLength - win) / hop - latencyHops;
-  // kept frame k starts at sample latencyHops hop - win - userPad + k hop; the kernels place frame t at
-  // t hop - win/2 + frameOffset
-  const int64_t frameOffset = latencyHops * hop - win + win / 2 - userPad;
+  // StreamingControl bookkeeping with the client's latency = win; only the kept frames are computed
+  const ControlFrames g = control_frames(n, win, hop, paddingMode, win);
+  const int64_t T = g.keep;
+  const int64_t frame0 = g.latencyHops * hop - win - g.userPad; // where kept frame 0 (analysis frame latencyHops) starts
   if (T < 1) return fail(ctx, "not enough frames");
   if (frames_out) *frames_out = T;
   const int64_t Tp = round_up(T, 32), Fp = round_up(F, 32);
@@ -298,11 +260,8 @@ static int features_common(fluhip_ctx* ctx, bool mfcc, const float* audio, int64
   const std::vector<int>& bandLo = mel.bandLo;
   const int64_t maxLen = mel.maxLen, nDct = mel.nDct;
   const int64_t nOut = mfcc ? nCoefs : nBands;
-  const double *wtab = nullptr, *ttab = nullptr;
-  rc = get_window(ctx, win, fft, FLUHIP_WINDOW_HANN, &wtab);
-  if (rc) return rc;
-  rc = get_twiddle(ctx, fft, &ttab);
-  if (rc) return rc;
+  StftSetup st;
+  if ((rc = stft_setup(ctx, win, fft, hop, &st))) return rc;
   DevBuf dFilt, dDct, dAudio, dMag, dOut, dLo, dPack;
   HIPCHK(ctx, dLo.alloc(bandLo.size() * sizeof(int), false, s));
   HIPCHK(ctx, dPack.alloc(wpack.size() * sizeof(double), false, s));
@@ -349,12 +308,7 @@ static int features_common(fluhip_ctx* ctx, bool mfcc, const float* audio, int64
           aPtr = dAud.as<float>();
         }
         float* oPtr = outDev ? out + b0 * nOut * T : dOutF.as<float>();
-        StftArgs sa;
-        sa.audio = aPtr; sa.audio64 = nullptr; sa.n = n; sa.audioStride = n;
-        sa.win = (int) win; sa.fft = (int) fft; sa.hop = (int) hop; sa.T = (int) T; sa.F = (int) F; sa.B = (int) nb;
-        sa.window = wtab; sa.twiddle = ttab;
-        sa.mag = nullptr; sa.magStride = 0; sa.ldMag = 0; sa.spec = nullptr; sa.specStride = 0;
-        sa.frameOffset = (int) frameOffset; sa.bigScratch = nullptr;
+        const StftArgs sa = st.args(aPtr, nullptr, n, n, nb, T, frame0);
         FeatArgs fa;
         fa.mag = nullptr; fa.magStride = 0; fa.ldMag = 0;
         fa.T = (int) T; fa.F = (int) F; fa.B = (int) nb; fa.win = (int) win;
@@ -397,18 +351,9 @@ static int features_common(fluhip_ctx* ctx, bool mfcc, const float* audio, int64
     const int64_t nb = std::min(chunk, count - b0);
     // hipMemcpyDefault: `audio` and `out` may be host or device pointers (a corpus already resident in HBM skips PCIe)
     HIPCHK(ctx, hipMemcpyAsync(dAudio.p, audio + b0 * n, (size_t) nb * n * sizeof(float), hipMemcpyDefault, s));
-    StftArgs sa;
-    sa.audio = dAudio.as<float>(); sa.audio64 = nullptr; sa.n = n; sa.audioStride = n;
-    sa.win = (int) win; sa.fft = (int) fft; sa.hop = (int) hop; sa.T = (int) T; sa.F = (int) F; sa.B = (int) nb;
-    sa.window = wtab; sa.twiddle = ttab;
+    StftArgs sa = st.args(dAudio.as<float>(), nullptr, n, n, nb, T, frame0);
     sa.mag = dMag.as<double>(); sa.magStride = Tp * Fp; sa.ldMag = Fp;
-    sa.spec = nullptr; sa.specStride = 0; sa.frameOffset = (int) frameOffset;
-    sa.bigScratch = big_fft_scratch(ctx, win, fft, nb * T);
-    if (stft_needs_scratch(win, fft) && !sa.bigScratch) return FLUHIP_ERROR;
-    {
-      ProfScope p(ctx, 0);
-      launch_stft(sa, s);
-    }
+    if ((rc = st.launch(ctx, sa, 0))) return rc;
     FeatArgs fa;
     fa.mag = dMag.as<double>(); fa.magStride = Tp * Fp; fa.ldMag = Fp;
     fa.T = (int) T; fa.F = (int) F; fa.B = (int) nb; fa.win = (int) win;
@@ -430,8 +375,8 @@ static int features_common(fluhip_ctx* ctx, bool mfcc, const float* audio, int64
   return FLUHIP_OK;
 }
 
-int fluhip_debug_features_plan(fluhip_ctx* ctx, int mfcc, int64_t win, int64_t fft, int64_t n_bands, int64_t n_coefs,
-                               int64_t start_coeff, double min_freq, double max_freq, double sample_rate, int64_t* out5)
+static int features_plan(fluhip_ctx* ctx, int mfcc, int64_t win, int64_t fft, int64_t n_bands, int64_t n_coefs,
+                         int64_t start_coeff, double min_freq, double max_freq, double sample_rate, int64_t* out5)
 {
   if (!out5) return fail(ctx, "null buffer");
   int rc = check_shape(ctx, 1, win, fft, 1, 1);
@@ -453,13 +398,39 @@ int fluhip_debug_features_plan(fluhip_ctx* ctx, int mfcc, int64_t win, int64_t f
   return FLUHIP_OK;
 }
 
+extern "C" {
+
+int fluhip_bufstft_forward_f32(fluhip_ctx* ctx, const float* audio, int64_t n, int64_t stride, int64_t win,
+                               int64_t fft, int64_t hop, int padding_mode, float* mag, float* phase,
+                               int64_t* hops_out)
+{
+  return guarded(ctx, [&] { return bufstft_forward(ctx, audio, n, stride, win, fft, hop, padding_mode, mag, phase, hops_out); });
+}
+
+int fluhip_bufstft_inverse_f32(fluhip_ctx* ctx, const float* mag, const float* phase, int64_t hops, int64_t win,
+                               int64_t fft, int64_t hop, int padding_mode, float* out, int64_t* n_out)
+{
+  return guarded(ctx, [&] { return bufstft_inverse(ctx, mag, phase, hops, win, fft, hop, padding_mode, out, n_out); });
+}
+
+int fluhip_debug_features_plan(fluhip_ctx* ctx, int mfcc, int64_t win, int64_t fft, int64_t n_bands, int64_t n_coefs,
+                               int64_t start_coeff, double min_freq, double max_freq, double sample_rate, int64_t* out5)
+{
+  fluhip_ctx host; // pure host arithmetic: a null context is accepted (an error then has no text to leave)
+  return guarded(ctx ? ctx : &host, [&] {
+    return features_plan(ctx, mfcc, win, fft, n_bands, n_coefs, start_coeff, min_freq, max_freq, sample_rate, out5);
+  });
+}
+
 int fluhip_bufmelbands_padded_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win,
                                   int64_t fft, int64_t hop, int64_t n_bands, double min_freq, double max_freq,
                                   double sample_rate, int normalize, int scale_db, int padding_mode, float* out,
                                   int64_t* frames_out)
 {
-  return features_common(ctx, false, audio, count, n, win, fft, hop, n_bands, 0, 0, min_freq, max_freq,
-                         sample_rate, normalize, scale_db, padding_mode, out, frames_out);
+  return guarded(ctx, [&] {
+    return features_common(ctx, false, audio, count, n, win, fft, hop, n_bands, 0, 0, min_freq, max_freq, sample_rate,
+                           normalize, scale_db, padding_mode, out, frames_out);
+  });
 }
 int fluhip_bufmelbands_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win,
                            int64_t fft, int64_t hop, int64_t n_bands, double min_freq, double max_freq,
@@ -473,8 +444,10 @@ int fluhip_bufmfcc_padded_f32(fluhip_ctx* ctx, const float* audio, int64_t count
                               int64_t hop, int64_t n_bands, int64_t n_coefs, int64_t start_coeff, double min_freq,
                               double max_freq, double sample_rate, int padding_mode, float* out, int64_t* frames_out)
 {
-  return features_common(ctx, true, audio, count, n, win, fft, hop, n_bands, n_coefs, start_coeff, min_freq,
-                         max_freq, sample_rate, 0, 0, padding_mode, out, frames_out);
+  return guarded(ctx, [&] {
+    return features_common(ctx, true, audio, count, n, win, fft, hop, n_bands, n_coefs, start_coeff, min_freq, max_freq,
+                           sample_rate, 0, 0, padding_mode, out, frames_out);
+  });
 }
 int fluhip_bufmfcc_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win, int64_t fft,
                        int64_t hop, int64_t n_bands, int64_t n_coefs, int64_t start_coeff, double min_freq,

@@ -12,24 +12,16 @@
 // and the closed form (numpy, under oracle/) and holds them against each other.
 #include "api_internal.h"
 
-extern "C" {
-
-int fluhip_nmfmatch_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win, int64_t fft, int64_t hop,
-                        const float* bases, int64_t K, int64_t seed, int padding_mode, float* out, int64_t* frames_out)
+static int nmfmatch_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win, int64_t fft, int64_t hop,
+                         const float* bases, int64_t K, int64_t seed, int padding_mode, float* out, int64_t* frames_out)
 {
-  if (!ctx) return FLUHIP_ERROR;
   if (!audio) return fail(ctx, "null buffer");
   if (padding_mode < 0 || padding_mode > 2) return fail(ctx, "padding mode must be 0 (None), 1 (Default) or 2 (Full)");
   if (count < 1) return fail(ctx, "need at least one channel");
   int rc = check_shape(ctx, n, win, fft, hop, K);
   if (rc) return rc;
-  // StreamingControl::process, cc/FluidNRTClientWrapper.hpp:557-579, 643-647
-  const int64_t pad = padding_mode == 0 ? 0 : padding_mode == 1 ? win >> 1 : win - hop; // FFTParams::padding
-  int64_t padded = n + win + 2 * pad;
-  if (padding_mode == 2) padded = ((padded + hop - 1) / hop) * hop;
-  const int64_t nAnalysis = 1 + (padded - win) / hop;
-  const int64_t latencyHops = win / hop;
-  const int64_t T = nAnalysis - latencyHops;
+  const ControlFrames g = control_frames(n, win, hop, padding_mode, win); // StreamingControl::process, latency = win
+  const int64_t pad = g.userPad, latencyHops = g.latencyHops, T = g.keep;
   if (frames_out) *frames_out = T;
   if (T < 1) return fail(ctx, "not enough frames");
   if (!out) return FLUHIP_OK; // size query
@@ -39,11 +31,8 @@ int fluhip_nmfmatch_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int6
   if (Ttot > 2000000000LL / 16) return fail(ctx, "too many frames");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const double *wtab = nullptr, *ttab = nullptr;
-  rc = get_window(ctx, win, fft, FLUHIP_WINDOW_HANN, &wtab);
-  if (rc) return rc;
-  rc = get_twiddle(ctx, fft, &ttab);
-  if (rc) return rc;
+  StftSetup st;
+  if ((rc = stft_setup(ctx, win, fft, hop, &st))) return rc;
 
   fluhip_corpus c;
   c.ctx = ctx; c.B = 1; c.K = K;
@@ -58,16 +47,9 @@ int fluhip_nmfmatch_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int6
   // of the frame of the call before -- FluidSource hands call j the window that ends where block j begins, padded samples
   // [j hop - win, j hop) -- so column k belongs to the frame at audio sample (k + latencyHops - 1) hop - win - pad
   // (rt/NMFMatchClient.hpp:104 writes the output, :108-117 then process the call's frame).
-  StftArgs sa;
-  sa.audio = in.as<float>(); sa.audio64 = nullptr; sa.n = n; sa.audioStride = n;
-  sa.win = (int) win; sa.fft = (int) fft; sa.hop = (int) hop; sa.T = (int) T; sa.F = (int) F; sa.B = (int) count;
-  sa.window = wtab; sa.twiddle = ttab;
+  StftArgs sa = st.args(in.as<float>(), nullptr, n, n, count, T, (latencyHops - 1) * hop - win - pad);
   sa.mag = c.mag.as<double>(); sa.magStride = T * c.Fp; sa.ldMag = c.Fp; // the channels' frames one after the other: one matrix
-  sa.spec = nullptr; sa.specStride = 0;
-  sa.frameOffset = (int) ((latencyHops - 1) * hop - win - pad + win / 2);
-  sa.bigScratch = big_fft_scratch(ctx, win, fft, Ttot);
-  if (stft_needs_scratch(win, fft) && !sa.bigScratch) return FLUHIP_ERROR;
-  launch_stft(sa, s);
+  if ((rc = st.launch(ctx, sa))) return rc;
   HIPCHK(ctx, hipGetLastError());
   // the filter buffer's channels as the client copies them (:100-101, float -> double)
   std::vector<double> W0((size_t) K * F);
@@ -91,10 +73,9 @@ int fluhip_nmfmatch_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int6
   return FLUHIP_OK;
 }
 
-int fluhip_nmffilter_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win, int64_t fft, int64_t hop,
-                         const float* bases, int64_t K, int64_t iters, int64_t seed, float* out)
+static int nmffilter_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win, int64_t fft, int64_t hop,
+                          const float* bases, int64_t K, int64_t iters, int64_t seed, float* out)
 {
-  if (!ctx) return FLUHIP_ERROR;
   if (!audio || !bases || !out) return fail(ctx, "null buffer");
   if (count < 1) return fail(ctx, "need at least one channel");
   if (iters < 0) return fail(ctx, "negative iteration count");
@@ -111,11 +92,8 @@ int fluhip_nmffilter_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int
   if (Ttot > 2000000000LL / 16) return fail(ctx, "too many frames");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const double *wtab = nullptr, *ttab = nullptr;
-  rc = get_window(ctx, win, fft, FLUHIP_WINDOW_HANN, &wtab);
-  if (rc) return rc;
-  rc = get_twiddle(ctx, fft, &ttab);
-  if (rc) return rc;
+  StftSetup st;
+  if ((rc = stft_setup(ctx, win, fft, hop, &st))) return rc;
 
   fluhip_corpus c;
   c.ctx = ctx; c.B = 1; c.K = K;
@@ -127,16 +105,10 @@ int fluhip_nmffilter_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int
   HIPCHK(ctx, hipMemcpyAsync(in.p, audio, (size_t) count * n * sizeof(float), hipMemcpyHostToDevice, s));
   HIPCHK(ctx, c.mag.alloc((size_t) c.Tp * c.Fp * sizeof(double), true, s));
   HIPCHK(ctx, spec.alloc((size_t) Ttot * F * 2 * sizeof(double), false, s));
-  StftArgs sa;
-  sa.audio = in.as<float>(); sa.audio64 = nullptr; sa.n = n; sa.audioStride = n;
-  sa.win = (int) win; sa.fft = (int) fft; sa.hop = (int) hop; sa.T = (int) T; sa.F = (int) F; sa.B = (int) count;
-  sa.window = wtab; sa.twiddle = ttab;
+  StftArgs sa = st.args(in.as<float>(), nullptr, n, n, count, T, hop - win); // frame t = m - 1 starts at (t + 1) hop - win
   sa.mag = c.mag.as<double>(); sa.magStride = T * c.Fp; sa.ldMag = c.Fp;
   sa.spec = spec.as<double>(); sa.specStride = T * F * 2;
-  sa.frameOffset = (int) (hop - win + win / 2); // frame t = m - 1 starts at (t + 1) hop - win
-  sa.bigScratch = big_fft_scratch(ctx, win, fft, Ttot);
-  if (stft_needs_scratch(win, fft) && !sa.bigScratch) return FLUHIP_ERROR;
-  launch_stft(sa, s);
+  if ((rc = st.launch(ctx, sa))) return rc;
   HIPCHK(ctx, hipGetLastError());
   std::vector<double> W0((size_t) K * F);
   for (size_t i = 0; i < W0.size(); i++) W0[i] = (double) bases[i];
@@ -153,25 +125,36 @@ int fluhip_nmffilter_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int
   {
     const double* Hb = c.H1.as<double>() + b * T * c.Kp;
     launch_vhat(c.Wf.as<double>(), 0, Hb, 0, vhat.as<double>(), F, 0, (int) T, (int) F, (int) c.Kp, 1, s); // NMF.hpp:87 v = W^T h
-    ResynthArgs ra;
-    ra.spec = spec.as<double>() + b * T * F * 2; ra.Wf = c.Wf.as<double>(); ra.H1 = Hb;
-    ra.Vhat = vhat.as<double>(); ra.ldV = F; ra.Kp = (int) c.Kp;
-    ra.win = (int) win; ra.fft = (int) fft; ra.hop = (int) hop; ra.T = (int) T; ra.F = (int) F;
-    ra.window = wtab; ra.twiddle = ttab; ra.frames = frames.as<double>(); ra.out = nullptr; ra.n = n; ra.outStride = n;
-    ra.trim = win - hop; // frame t lies at [t hop - trim, t hop - trim + win) of the output
+    // frame t lies at [t hop - trim, t hop - trim + win) of the output, trim = win - hop
+    ResynthArgs ra = st.resynth(spec.as<double>() + b * T * F * 2, T, frames.as<double>(), n, win - hop);
+    ra.Wf = c.Wf.as<double>(); ra.H1 = Hb; ra.Vhat = vhat.as<double>(); ra.ldV = F; ra.Kp = (int) c.Kp; ra.outStride = n;
     for (int64_t k = 0; k < K; k += compsPerLaunch)
     {
       ra.k = (int) k;
       ra.nComp = (int) std::min(compsPerLaunch, K - k);
       ra.out32 = dout.as<float>() + (b * K + k) * n;
-      ra.bigScratch = big_fft_scratch(ctx, ra.win, ra.fft, ra.T);
-      if (stft_needs_scratch(ra.win, ra.fft) && !ra.bigScratch) return FLUHIP_ERROR;
-      launch_resynth(ra, s);
+      if ((rc = st.launch(ctx, ra))) return rc;
     }
   }
   HIPCHK(ctx, hipGetLastError());
   const size_t nbytes = (size_t) count * K * n * sizeof(float);
   return copy_to_host(ctx, out, nbytes, dout.p, nbytes, nbytes, 1, s);
+}
+
+extern "C" {
+
+int fluhip_nmfmatch_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win, int64_t fft, int64_t hop,
+                        const float* bases, int64_t K, int64_t seed, int padding_mode, float* out, int64_t* frames_out)
+{
+  return guarded(ctx, [&] {
+    return nmfmatch_impl(ctx, audio, count, n, win, fft, hop, bases, K, seed, padding_mode, out, frames_out);
+  });
+}
+
+int fluhip_nmffilter_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win, int64_t fft, int64_t hop,
+                         const float* bases, int64_t K, int64_t iters, int64_t seed, float* out)
+{
+  return guarded(ctx, [&] { return nmffilter_impl(ctx, audio, count, n, win, fft, hop, bases, K, iters, seed, out); });
 }
 
 } // extern "C"

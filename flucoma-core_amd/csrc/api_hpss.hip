@@ -6,33 +6,7 @@
 #include "api_internal.h"
 #include "fluhip_hpss.h"
 
-#include <new>
-
 namespace {
-
-template <typename Fn> int guarded_hpss(fluhip_ctx* ctx, Fn&& fn)
-{
-  if (!ctx) return FLUHIP_ERROR;
-  try
-  {
-    return fn();
-  }
-  catch (const std::bad_alloc&)
-  {
-    return fail_oom(ctx, "host allocation failed");
-  }
-  catch (...)
-  {
-    return fail(ctx, "internal error");
-  }
-}
-
-#define HALLOC(ctx, buf, bytes, zero)                                                              \
-  do                                                                                               \
-  {                                                                                                \
-    hipError_t e__ = (buf).alloc((bytes), (zero), (ctx)->stream);                                  \
-    if (e__ != hipSuccess) return fail_hip((ctx), e__, "device allocation of the HPSS workspace"); \
-  } while (0)
 
 constexpr int64_t kHpssCapDoubles = (int64_t) 1 << 27; // 1 GiB of planes and spectra per round
 constexpr int64_t kHpssMaxFilter = 1001;               // the count is O(size^2) per value: a bound on what one launch may cost
@@ -96,7 +70,7 @@ int upload_thresholds(fluhip_ctx* ctx, int64_t F, const double* hThresh, const d
   std::vector<double> thr = make_threshold(F, hThresh);
   const std::vector<double> p = make_threshold(F, pThresh);
   thr.insert(thr.end(), p.begin(), p.end());
-  HALLOC(ctx, dThr, thr.size() * sizeof(double), false);
+  DEV_ALLOC(ctx, "HPSS", dThr, thr.size() * sizeof(double), false);
   HIPCHK(ctx, hipMemcpyAsync(dThr.p, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // (thr is a local)
   return FLUHIP_OK;
@@ -123,9 +97,9 @@ int hpss_planes_impl(fluhip_ctx* ctx, const double* mag, int64_t count, int64_t 
   if ((rc = upload_thresholds(ctx, F, hThresh, pThresh, dThr))) return rc;
   const int64_t perBuffer = T * (ld + nOut * F);
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(count, kHpssCapDoubles / perBuffer));
-  HALLOC(ctx, dMag, (size_t) (chunk * T * ld) * sizeof(double), false);
+  DEV_ALLOC(ctx, "HPSS", dMag, (size_t) (chunk * T * ld) * sizeof(double), false);
   for (int i = 0; i < 5; i++)
-    if (outs[i]) HALLOC(ctx, dOut[i], (size_t) (chunk * T * F) * sizeof(double), false);
+    if (outs[i]) DEV_ALLOC(ctx, "HPSS", dOut[i], (size_t) (chunk * T * F) * sizeof(double), false);
   for (int64_t b0 = 0; b0 < count; b0 += chunk)
   {
     const int64_t nb = std::min(chunk, count - b0);
@@ -173,39 +147,29 @@ int bufhpss_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, 
   if (count > (INT64_MAX / 64) / std::max(T * (ldM + 8 * F), n)) return fail(ctx, "batch too large");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const double *wtab = nullptr, *ttab = nullptr;
-  if ((rc = get_window(ctx, win, fft, FLUHIP_WINDOW_HANN, &wtab))) return rc;
-  if ((rc = get_twiddle(ctx, fft, &ttab))) return rc;
+  StftSetup st;
+  if ((rc = stft_setup(ctx, win, fft, hop, &st))) return rc;
   DevBuf dThr, dIn, dMag, dSpec, dMasked, dFrames, dOut;
   if ((rc = upload_thresholds(ctx, F, hThresh, pThresh, dThr))) return rc;
   // buffers per round: magnitudes, the spectrum and the three masked spectra of a round stay below the cap
   const int64_t perBuffer = T * (ldM + 8 * F);
   int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(count, kHpssCapDoubles / perBuffer));
   chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (2000000000LL / 16) / T));
-  HALLOC(ctx, dIn, (size_t) (chunk * n) * sizeof(float), false);
-  HALLOC(ctx, dMag, (size_t) (chunk * T * ldM) * sizeof(double), false);
-  HALLOC(ctx, dSpec, (size_t) (chunk * T * F * 2) * sizeof(double), false);
-  HALLOC(ctx, dMasked, (size_t) (chunk * 3 * T * F * 2) * sizeof(double), false);
-  HALLOC(ctx, dFrames, (size_t) (T * win) * sizeof(double), false);
-  HALLOC(ctx, dOut, (size_t) (chunk * 3 * n) * sizeof(float), false);
+  DEV_ALLOC(ctx, "HPSS", dIn, (size_t) (chunk * n) * sizeof(float), false);
+  DEV_ALLOC(ctx, "HPSS", dMag, (size_t) (chunk * T * ldM) * sizeof(double), false);
+  DEV_ALLOC(ctx, "HPSS", dSpec, (size_t) (chunk * T * F * 2) * sizeof(double), false);
+  DEV_ALLOC(ctx, "HPSS", dMasked, (size_t) (chunk * 3 * T * F * 2) * sizeof(double), false);
+  DEV_ALLOC(ctx, "HPSS", dFrames, (size_t) (T * win) * sizeof(double), false);
+  DEV_ALLOC(ctx, "HPSS", dOut, (size_t) (chunk * 3 * n) * sizeof(float), false);
   const int nInverse = mode == 2 ? 3 : 2; // the residual mask is zero in modes 0 and 1: its output is zeros, no transform
   for (int64_t b0 = 0; b0 < count; b0 += chunk)
   {
     const int64_t nb = std::min(chunk, count - b0);
     HIPCHK(ctx, hipMemcpyAsync(dIn.p, audio + b0 * n, (size_t) (nb * n) * sizeof(float), hipMemcpyHostToDevice, s));
-    StftArgs sa;
-    sa.audio = dIn.as<float>(); sa.audio64 = nullptr; sa.n = n; sa.audioStride = n;
-    sa.win = (int) win; sa.fft = (int) fft; sa.hop = (int) hop; sa.T = (int) T; sa.F = (int) F; sa.B = (int) nb;
-    sa.window = wtab; sa.twiddle = ttab;
+    StftArgs sa = st.args(dIn.as<float>(), nullptr, n, n, nb, T, hop - win); // frame t = m - 1 starts at (t + 1) hop - win: every one touches the buffer
     sa.mag = dMag.as<double>(); sa.magStride = T * ldM; sa.ldMag = ldM;
     sa.spec = dSpec.as<double>(); sa.specStride = T * F * 2;
-    sa.frameOffset = (int) (hop - win + win / 2); // frame t = m - 1 starts at (t + 1) hop - win: every one touches the buffer
-    sa.bigScratch = big_fft_scratch(ctx, win, fft, nb * T);
-    if (stft_needs_scratch(win, fft) && !sa.bigScratch) return FLUHIP_ERROR;
-    {
-      ProfScope p(ctx, 0);
-      launch_stft(sa, s);
-    }
+    if ((rc = st.launch(ctx, sa, 0))) return rc;
     HIPCHK(ctx, hipGetLastError());
     HpssArgs a;
     a.mag = dMag.as<double>(); a.magStride = T * ldM; a.ldMag = ldM;
@@ -229,16 +193,10 @@ int bufhpss_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, 
         for (int c = 0; c < nInverse; c++)
         {
           // ISTFT::processFrame per frame, overlap-add, division by the overlap-added window^2 (BufferedProcess.hpp:219-239)
-          ResynthArgs ra;
-          ra.spec = dMasked.as<double>() + (b * 3 + c) * T * F * 2; ra.Wf = nullptr; ra.H1 = nullptr;
-          ra.Vhat = nullptr; ra.ldV = 0; ra.Kp = 0; ra.k = 0; ra.nComp = 1;
-          ra.win = (int) win; ra.fft = (int) fft; ra.hop = (int) hop; ra.T = (int) T; ra.F = (int) F;
-          ra.window = wtab; ra.twiddle = ttab; ra.frames = dFrames.as<double>(); ra.out = nullptr;
-          ra.out32 = dOut.as<float>() + (b * 3 + c) * n; ra.n = n; ra.outStride = n;
-          ra.trim = win - hop; // frame t lies at [t hop - trim, t hop - trim + win) of the output
-          ra.bigScratch = big_fft_scratch(ctx, ra.win, ra.fft, ra.T);
-          if (stft_needs_scratch(ra.win, ra.fft) && !ra.bigScratch) return FLUHIP_ERROR;
-          launch_resynth(ra, s);
+          // frame t lies at [t hop - trim, t hop - trim + win) of the output, trim = win - hop
+          ResynthArgs ra = st.resynth(dMasked.as<double>() + (b * 3 + c) * T * F * 2, T, dFrames.as<double>(), n, win - hop);
+          ra.out32 = dOut.as<float>() + (b * 3 + c) * n; ra.outStride = n;
+          if ((rc = st.launch(ctx, ra))) return rc;
         }
     }
     HIPCHK(ctx, hipGetLastError());
@@ -270,7 +228,7 @@ int fluhip_hpss_planes_f64(fluhip_ctx* ctx, const double* mag, int64_t count, in
                            int64_t harm_filter_size, int64_t perc_filter_size, int mode, const double* harm_thresh,
                            const double* perc_thresh, double* hmed, double* vmed, double* const* masks)
 {
-  return guarded_hpss(ctx, [&] {
+  return guarded(ctx, [&] {
     return hpss_planes_impl(ctx, mag, count, T, F, ld, harm_filter_size, perc_filter_size, mode, harm_thresh, perc_thresh, hmed,
                             vmed, masks);
   });
@@ -280,7 +238,7 @@ int fluhip_bufhpss_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64
                        int64_t harm_filter_size, int64_t perc_filter_size, int mode, const double* harm_thresh,
                        const double* perc_thresh, float* out)
 {
-  return guarded_hpss(ctx, [&] {
+  return guarded(ctx, [&] {
     return bufhpss_impl(ctx, audio, count, n, win, fft, hop, harm_filter_size, perc_filter_size, mode, harm_thresh, perc_thresh, out);
   });
 }

@@ -1,9 +1,12 @@
 // api_internal.h -- what the translation units of the C-ABI layer share (api_core / api_corpus / api_algorithms /
-// api_features / api_frames .hip): the context and corpus structures, the caching device buffer, and the helpers one
-// unit defines for the others.  Not installed; nothing here is part of the ABI (hidden visibility).
+// api_features / api_frames / api_cross / api_novelty / api_onset / api_hpss / api_pitch .hip): the context and corpus
+// structures, the caching device buffer, the scaffold of a call (guarded, DEV_ALLOC, check_fft_settings, StftSetup) and the
+// helpers one unit defines for the others.  The clients' frame counts are in client_frames.h (host only, shared with
+// api_pool.cpp).  Not installed; nothing here is part of the ABI (hidden visibility).
 #pragma once
 
 #include "../../include/flucoma_hip.h"
+#include "client_frames.h"
 #include "fluhip_kernels.h"
 
 #include <algorithm>
@@ -15,6 +18,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <optional>
 #include <random>
 #include <string>
@@ -67,6 +71,33 @@ int fail_hip(fluhip_ctx* ctx, hipError_t e, const char* what);
   {                                                                                              \
     hipError_t e__ = (expr);                                                                     \
     if (e__ != hipSuccess) return fail_hip(ctx, e__, #expr);                                     \
+  } while (0)
+
+// The body of an extern "C" entry point: nothing thrown on the host (std::vector images, filter-bank tables) may cross the
+// C ABI.  std::bad_alloc is an out-of-memory failure like a device allocation, anything else an internal error.
+template <typename Fn> int guarded(fluhip_ctx* ctx, Fn&& fn)
+{
+  if (!ctx) return FLUHIP_ERROR;
+  try
+  {
+    return fn();
+  }
+  catch (const std::bad_alloc&)
+  {
+    return fail_oom(ctx, "host allocation failed");
+  }
+  catch (...)
+  {
+    return fail(ctx, "internal error");
+  }
+}
+
+// buf.alloc on the context's stream, or return "... device allocation of the <what> workspace" (what: a string literal)
+#define DEV_ALLOC(ctx, what, buf, bytes, zero)                                                              \
+  do                                                                                                        \
+  {                                                                                                         \
+    hipError_t e__ = (buf).alloc((bytes), (zero), (ctx)->stream);                                           \
+    if (e__ != hipSuccess) return fail_hip((ctx), e__, "device allocation of the " what " workspace");      \
   } while (0)
 
 // api_core.hip
@@ -216,6 +247,45 @@ struct ProfScope
     ctx->profRecs.push_back(rec);
   }
 };
+
+// The window and twiddle tables of one (win, fft, hop) and the two transforms launched with them (stft_setup, api_core.hip).
+struct StftSetup
+{
+  int64_t win = 0, fft = 0, hop = 0, F = 0;
+  const double* window = nullptr;  // device, [max(win, fft)], zero past win
+  const double* twiddle = nullptr; // device, [fft / 2]
+  // B buffers of n samples, `stride` apart (a32 or a64, the other null), as T frames each.  frame0 is the sample of its
+  // buffer at which frame 0 starts (frame t: frame0 + t hop; samples outside [0, n) read as zero): -(win / 2) for
+  // STFT::process' centred frames, j hop - win - userPad for analysis frame j of a control client (client_frames.h).
+  // This is the one place that turns it into the kernels' frameOffset.  mag / spec and their strides are the caller's.
+  StftArgs args(const float* a32, const double* a64, int64_t n, int64_t stride, int64_t B, int64_t T, int64_t frame0) const
+  {
+    StftArgs a;
+    a.audio = a32; a.audio64 = a64; a.n = n; a.audioStride = stride;
+    a.win = (int) win; a.fft = (int) fft; a.hop = (int) hop; a.T = (int) T; a.F = (int) F; a.B = (int) B;
+    a.window = window; a.twiddle = twiddle;
+    a.frameOffset = (int) (win / 2 + frame0);
+    return a;
+  }
+  // launch_stft of `a` on the context's stream, with the global-memory workspace of fft > 8192 looked up for its B T frames;
+  // profClass >= 0: inside a ProfScope of that class.  The on-chip forms (launch_onset_fused, launch_pitch_fused,
+  // launch_stft_features, launch_stft_block) take the same `a` and need none of this.
+  int launch(fluhip_ctx* ctx, StftArgs a, int profClass = -1) const;
+  // plain inverse transform + overlap-add of spec [T][F] through frames [T][win] into n samples, the first `trim` dropped;
+  // the caller adds the output pointer(s) and, for the masked form, Wf / H1 / Vhat / k / nComp
+  ResynthArgs resynth(const double* spec, int64_t T, double* frames, int64_t n, int64_t trim) const
+  {
+    ResynthArgs r;
+    r.spec = spec; r.frames = frames; r.n = n; r.trim = trim;
+    r.win = (int) win; r.fft = (int) fft; r.hop = (int) hop; r.T = (int) T; r.F = (int) F;
+    r.window = window; r.twiddle = twiddle;
+    return r;
+  }
+  int launch(fluhip_ctx* ctx, ResynthArgs r) const; // launch_resynth, workspace as above
+};
+int stft_setup(fluhip_ctx* ctx, int64_t win, int64_t fft, int64_t hop, StftSetup* out, int windowType = FLUHIP_WINDOW_HANN);
+// the clients' FFTParams constraints, with their "fftSettings: ..." texts
+int check_fft_settings(fluhip_ctx* ctx, int64_t win, int64_t fft, int64_t hop);
 
 // ---------------------------------------------------------------------------------------
 // corpus

@@ -8,33 +8,7 @@
 #include "api_internal.h"
 #include "fluhip_novelty.h"
 
-#include <new>
-
 namespace {
-
-template <typename Fn> int guarded_novelty(fluhip_ctx* ctx, Fn&& fn)
-{
-  if (!ctx) return FLUHIP_ERROR;
-  try
-  {
-    return fn();
-  }
-  catch (const std::bad_alloc&)
-  {
-    return fail_oom(ctx, "host allocation failed");
-  }
-  catch (...)
-  {
-    return fail(ctx, "internal error");
-  }
-}
-
-#define NALLOC(ctx, buf, bytes, zero)                                                                \
-  do                                                                                                 \
-  {                                                                                                  \
-    hipError_t e__ = (buf).alloc((bytes), (zero), (ctx)->stream);                                    \
-    if (e__ != hipSuccess) return fail_hip((ctx), e__, "device allocation of the novelty workspace"); \
-  } while (0)
 
 constexpr int64_t kMaxFilterSize = (int64_t) 1 << 20; // the moving mean is O(filterSize) per value; the latency stays far inside int64
 
@@ -70,9 +44,9 @@ int novelty_curve_dev(fluhip_ctx* ctx, const double* X, int64_t ldx, int64_t str
   const int64_t cap = one.form == kNoveltyFormTiled ? ((int64_t) 1 << 28) : ((int64_t) 1 << 30);
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(count, cap / std::max<int64_t>(per, 1)));
   DevBuf nov, work;
-  NALLOC(ctx, nov, (size_t) (chunk * T) * sizeof(double), false);
+  DEV_ALLOC(ctx, "novelty", nov, (size_t) (chunk * T) * sizeof(double), false);
   const NoveltyPlan full = novelty_plan(chunk, T, D, k);
-  if (full.workDoubles) NALLOC(ctx, work, (size_t) full.workDoubles * sizeof(double), false);
+  if (full.workDoubles) DEV_ALLOC(ctx, "novelty", work, (size_t) full.workDoubles * sizeof(double), false);
   for (int64_t b0 = 0; b0 < count; b0 += chunk)
   {
     const int64_t nb = std::min(chunk, count - b0);
@@ -120,15 +94,15 @@ int novelty_slices_impl(fluhip_ctx* ctx, const double* feat, int64_t count, int6
     HIPCHK(ctx, hipStreamSynchronize(s));
     return FLUHIP_OK;
   }
-  NALLOC(ctx, dX, (size_t) (count * T * D) * sizeof(double), false);
-  NALLOC(ctx, dCurve, (size_t) (count * T) * sizeof(double), false);
+  DEV_ALLOC(ctx, "novelty", dX, (size_t) (count * T * D) * sizeof(double), false);
+  DEV_ALLOC(ctx, "novelty", dCurve, (size_t) (count * T) * sizeof(double), false);
   HIPCHK(ctx, hipMemcpy2DAsync(dX.p, (size_t) D * sizeof(double), feat, (size_t) ld * sizeof(double), (size_t) D * sizeof(double),
                                (size_t) (count * T), hipMemcpyDefault, s));
   if ((rc = novelty_curve_dev(ctx, dX.as<double>(), D, T * D, count, T, D, k, f, dCurve.as<double>()))) return rc;
   if (slices)
   {
-    NALLOC(ctx, dDet, (size_t) (count * T), false);
-    NALLOC(ctx, dCnt, (size_t) count * sizeof(int64_t), false);
+    DEV_ALLOC(ctx, "novelty", dDet, (size_t) (count * T), false);
+    DEV_ALLOC(ctx, "novelty", dCnt, (size_t) count * sizeof(int64_t), false);
     launch_novelty_peaks(dCurve.as<double>(), (int) T, count, threshold, (int) std::min<int64_t>(minSlice, INT32_MAX), dDet.as<unsigned char>(),
                          dCnt.as<int64_t>(), s);
     HIPCHK(ctx, hipGetLastError());
@@ -154,7 +128,7 @@ struct NoveltyFeatures
   int algorithm;
   int64_t n, win, fft, hop, T, F, Tp, Fp, shift;
   double sampleRate;
-  const double *wtab = nullptr, *ttab = nullptr;
+  StftSetup st;
   DevBuf mag, coef, dLo, dPack, dFilt, dDct;
   MelTables mel;
   int64_t chunk = 1; // buffers per round
@@ -166,21 +140,20 @@ struct NoveltyFeatures
   {
     hipStream_t s = ctx->stream;
     F = fft / 2 + 1; Tp = round_up(T, 32); Fp = round_up(F, 32);
-    int rc = get_window(ctx, win, fft, FLUHIP_WINDOW_HANN, &wtab);
+    const int rc = stft_setup(ctx, win, fft, hop, &st);
     if (rc) return rc;
-    if ((rc = get_twiddle(ctx, fft, &ttab))) return rc;
     const int64_t perBuf = Tp * Fp * (int64_t) sizeof(double);
     chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(count, 65535), ((int64_t) 2 << 30) / perBuf));
-    NALLOC(ctx, mag, (size_t) (chunk * perBuf), true);
+    DEV_ALLOC(ctx, "novelty", mag, (size_t) (chunk * perBuf), true);
     if (algorithm == 1)
     {
       // mMelBands.init(20, 20e3, 40, frameSize, sampleRate, winSize); mDCT.init(40, 13) (rt/NoveltySliceClient.hpp:112-116)
       mel.build(true, F, kBands, kBandsPad, kCoefs, 0, 20.0, 20e3, sampleRate);
-      NALLOC(ctx, coef, (size_t) (chunk * T * kCoefs) * sizeof(double), false);
-      NALLOC(ctx, dLo, mel.bandLo.size() * sizeof(int), false);
-      NALLOC(ctx, dPack, mel.wpack.size() * sizeof(double), false);
-      NALLOC(ctx, dFilt, mel.filtT.size() * sizeof(double), false);
-      NALLOC(ctx, dDct, mel.dct.size() * sizeof(double), false);
+      DEV_ALLOC(ctx, "novelty", coef, (size_t) (chunk * T * kCoefs) * sizeof(double), false);
+      DEV_ALLOC(ctx, "novelty", dLo, mel.bandLo.size() * sizeof(int), false);
+      DEV_ALLOC(ctx, "novelty", dPack, mel.wpack.size() * sizeof(double), false);
+      DEV_ALLOC(ctx, "novelty", dFilt, mel.filtT.size() * sizeof(double), false);
+      DEV_ALLOC(ctx, "novelty", dDct, mel.dct.size() * sizeof(double), false);
       HIPCHK(ctx, hipMemcpyAsync(dLo.p, mel.bandLo.data(), mel.bandLo.size() * sizeof(int), hipMemcpyHostToDevice, s));
       HIPCHK(ctx, hipMemcpyAsync(dPack.p, mel.wpack.data(), mel.wpack.size() * sizeof(double), hipMemcpyHostToDevice, s));
       HIPCHK(ctx, hipMemcpyAsync(dFilt.p, mel.filtT.data(), mel.filtT.size() * sizeof(double), hipMemcpyHostToDevice, s));
@@ -193,16 +166,9 @@ struct NoveltyFeatures
   int run(const float* audioDev, int64_t nb, const double** rows, int64_t* ldx, int64_t* strideX)
   {
     hipStream_t s = ctx->stream;
-    StftArgs sa;
-    sa.audio = audioDev; sa.audio64 = nullptr; sa.n = n; sa.audioStride = n;
-    sa.win = (int) win; sa.fft = (int) fft; sa.hop = (int) hop; sa.T = (int) T; sa.F = (int) F; sa.B = (int) nb;
-    sa.window = wtab; sa.twiddle = ttab;
+    StftArgs sa = st.args(audioDev, nullptr, n, n, nb, T, -win - shift);
     sa.mag = mag.as<double>(); sa.magStride = Tp * Fp; sa.ldMag = Fp;
-    sa.spec = nullptr; sa.specStride = 0;
-    sa.frameOffset = (int) (win / 2 - win - shift); // the kernels place frame t at t hop - win / 2 + frameOffset
-    sa.bigScratch = big_fft_scratch(ctx, win, fft, nb * T);
-    if (stft_needs_scratch(win, fft) && !sa.bigScratch) return FLUHIP_ERROR;
-    launch_stft(sa, s);
+    if (const int rc = st.launch(ctx, sa)) return rc;
     *rows = mag.as<double>(); *ldx = Fp; *strideX = Tp * Fp;
     if (algorithm == 1)
     {
@@ -253,18 +219,17 @@ int bufnoveltyslice_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int
   // Slicing::process (:675-723): latency zeros behind the input, rounded up to whole host vectors of 64; a frame fires at
   // every multiple of hop below that length
   const int64_t latency = novelty_latency(hop, k, f);
-  const int64_t padded = (n + latency + 63) / 64 * 64;
-  const int64_t T = (padded + hop - 1) / hop;
+  const int64_t T = slice_frames(n, hop, latency).T;
   if (T > INT32_MAX / 4) return fail(ctx, "too many frames");
   NoveltyFeatures nf{ctx, algorithm, n, win, fft, hop, T, 0, 0, 0, 0, sampleRate};
   if ((rc = nf.prepare(count))) return rc;
   const int64_t chunk = nf.chunk;
   DevBuf dIn, dMono, dCurve, dDet, dCnt;
-  NALLOC(ctx, dIn, (size_t) (chunk * channels * n) * sizeof(float), false);
-  if (channels > 1) NALLOC(ctx, dMono, (size_t) (chunk * n) * sizeof(float), false);
-  NALLOC(ctx, dCurve, (size_t) (chunk * T) * sizeof(double), false);
-  NALLOC(ctx, dDet, (size_t) (chunk * T), false);
-  NALLOC(ctx, dCnt, (size_t) chunk * sizeof(int64_t), false);
+  DEV_ALLOC(ctx, "novelty", dIn, (size_t) (chunk * channels * n) * sizeof(float), false);
+  if (channels > 1) DEV_ALLOC(ctx, "novelty", dMono, (size_t) (chunk * n) * sizeof(float), false);
+  DEV_ALLOC(ctx, "novelty", dCurve, (size_t) (chunk * T) * sizeof(double), false);
+  DEV_ALLOC(ctx, "novelty", dDet, (size_t) (chunk * T), false);
+  DEV_ALLOC(ctx, "novelty", dCnt, (size_t) chunk * sizeof(int64_t), false);
   std::vector<unsigned char> det((size_t) (count * T));
   for (int64_t b0 = 0; b0 < count; b0 += chunk)
   {
@@ -286,26 +251,9 @@ int bufnoveltyslice_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int
     HIPCHK(ctx, hipMemcpyAsync(det.data() + b0 * T, dDet.p, (size_t) (nb * T), hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
   }
-  // Slicing::process :709-722 + spikesToTimes: the detection of frame i stands at sample i hop of the padded signal
   for (int64_t b = 0; b < count; b++)
-  {
-    const unsigned char* d = det.data() + b * T;
-    int64_t* out = indices ? indices + b * capacity : nullptr;
-    int64_t cnt = 0;
-    auto put = [&](int64_t v) { if (cnt < capacity) out[cnt] = v; cnt++; };
-    bool early = false;
-    for (int64_t i = 0; i < T && i * hop < latency; i++) early = early || d[i];
-    const bool atLatency = (latency % hop) == 0 && latency / hop < T && d[latency / hop];
-    if ((early || atLatency) && n > 0) put(startFrame);
-    for (int64_t i = latency / hop + 1; i < T; i++)
-    {
-      const int64_t p = i * hop - latency;
-      if (p >= n) break;
-      if (d[i]) put(p + startFrame);
-    }
-    if (cnt == 0) put(-1);
-    counts[b] = cnt;
-  }
+    counts[b] = detections_to_indices(det.data() + b * T, T, hop, latency, n, startFrame, indices ? indices + b * capacity : nullptr,
+                                      capacity);
   return FLUHIP_OK;
 }
 
@@ -322,14 +270,9 @@ int bufnoveltyfeature_impl(fluhip_ctx* ctx, const float* audio, int64_t count, i
   if ((rc = check_client_shape(ctx, algorithm, n, win, fft, hop))) return rc;
   // StreamingControl::process (:564-579, 642-656): the input sits userPad into the padded signal, frame j fires with the
   // j-th host vector of hop samples, the first latency / hop frames are dropped
-  const int64_t latency = novelty_latency(hop, k, f), latencyHops = latency / hop;
-  const int64_t userPad = paddingMode == 0 ? 0 : paddingMode == 1 ? win / 2 : win - hop;
-  int64_t paddedLength = n + latency + 2 * userPad;
-  if (paddingMode == 2) paddedLength = ((paddedLength + hop - 1) / hop) * hop;
-  if (paddedLength < win) return fail(ctx, "not enough frames");
-  const int64_t T = 1 + (paddedLength - win) / hop;
-  const int64_t keep = T - latencyHops;
-  if (keep < 1) return fail(ctx, "not enough frames");
+  const ControlFrames g = control_frames(n, win, hop, paddingMode, novelty_latency(hop, k, f));
+  const int64_t userPad = g.userPad, T = g.T, latencyHops = g.latencyHops, keep = g.keep;
+  if (g.paddedLength < win || keep < 1) return fail(ctx, "not enough frames");
   if (T > INT32_MAX / 4) return fail(ctx, "too many frames");
   if (framesOut) *framesOut = keep;
   if (!out) return FLUHIP_OK; // size query
@@ -339,9 +282,9 @@ int bufnoveltyfeature_impl(fluhip_ctx* ctx, const float* audio, int64_t count, i
   if ((rc = nf.prepare(count))) return rc;
   const int64_t chunk = nf.chunk;
   DevBuf dIn, dCurve, dOut;
-  NALLOC(ctx, dIn, (size_t) (chunk * n) * sizeof(float), false);
-  NALLOC(ctx, dCurve, (size_t) (chunk * T) * sizeof(double), false);
-  NALLOC(ctx, dOut, (size_t) (chunk * keep) * sizeof(float), false);
+  DEV_ALLOC(ctx, "novelty", dIn, (size_t) (chunk * n) * sizeof(float), false);
+  DEV_ALLOC(ctx, "novelty", dCurve, (size_t) (chunk * T) * sizeof(double), false);
+  DEV_ALLOC(ctx, "novelty", dOut, (size_t) (chunk * keep) * sizeof(float), false);
   for (int64_t b0 = 0; b0 < count; b0 += chunk)
   {
     const int64_t nb = std::min(chunk, count - b0);
@@ -375,7 +318,7 @@ int fluhip_debug_novelty_plan(fluhip_ctx* ctx, int64_t T, int64_t D, int64_t ker
 int fluhip_novelty_curve_f64(fluhip_ctx* ctx, const double* feat, int64_t count, int64_t T, int64_t D, int64_t ld,
                              int64_t kernel_size, int64_t filter_size, double* curve)
 {
-  return guarded_novelty(ctx, [&] {
+  return guarded(ctx, [&] {
     return novelty_slices_impl(ctx, feat, count, T, D, ld, kernel_size, filter_size, 0.0, 0, false, nullptr, nullptr, curve);
   });
 }
@@ -384,7 +327,7 @@ int fluhip_novelty_slices_f64(fluhip_ctx* ctx, const double* feat, int64_t count
                               int64_t kernel_size, int64_t filter_size, double threshold, int64_t min_slice,
                               unsigned char* det, int64_t* counts, double* curve)
 {
-  return guarded_novelty(ctx, [&] {
+  return guarded(ctx, [&] {
     return novelty_slices_impl(ctx, feat, count, T, D, ld, kernel_size, filter_size, threshold, min_slice, true, det, counts,
                                curve);
   });
@@ -395,7 +338,7 @@ int fluhip_bufnoveltyslice_f32(fluhip_ctx* ctx, const float* audio, int64_t coun
                                int64_t filter_size, int64_t min_slice, int64_t win, int64_t fft, int64_t hop,
                                double sample_rate, int64_t* indices, int64_t capacity, int64_t* counts)
 {
-  return guarded_novelty(ctx, [&] {
+  return guarded(ctx, [&] {
     return bufnoveltyslice_impl(ctx, audio, count, channels, n, start_frame, algorithm, kernel_size, threshold, filter_size,
                                 min_slice, win, fft, hop, sample_rate, indices, capacity, counts);
   });
@@ -405,7 +348,7 @@ int fluhip_bufnoveltyfeature_f32(fluhip_ctx* ctx, const float* audio, int64_t co
                                  int64_t kernel_size, int64_t filter_size, int64_t win, int64_t fft, int64_t hop,
                                  double sample_rate, int padding_mode, float* out, int64_t* frames_out)
 {
-  return guarded_novelty(ctx, [&] {
+  return guarded(ctx, [&] {
     return bufnoveltyfeature_impl(ctx, audio, count, n, algorithm, kernel_size, filter_size, win, fft, hop, sample_rate,
                                   padding_mode, out, frames_out);
   });

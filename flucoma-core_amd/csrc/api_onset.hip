@@ -9,33 +9,7 @@
 #include "fluhip_novelty.h" // launch_mono_sum_f32, launch_curve_to_f32
 #include "fluhip_onset.h"
 
-#include <new>
-
 namespace {
-
-template <typename Fn> int guarded_onset(fluhip_ctx* ctx, Fn&& fn)
-{
-  if (!ctx) return FLUHIP_ERROR;
-  try
-  {
-    return fn();
-  }
-  catch (const std::bad_alloc&)
-  {
-    return fail_oom(ctx, "host allocation failed");
-  }
-  catch (...)
-  {
-    return fail(ctx, "internal error");
-  }
-}
-
-#define OALLOC(ctx, buf, bytes, zero)                                                              \
-  do                                                                                               \
-  {                                                                                                \
-    hipError_t e__ = (buf).alloc((bytes), (zero), (ctx)->stream);                                  \
-    if (e__ != hipSuccess) return fail_hip((ctx), e__, "device allocation of the onset workspace"); \
-  } while (0)
 
 constexpr int64_t kSpecCapDoubles = (int64_t) 1 << 27; // 1 GiB of spectra per round
 
@@ -46,10 +20,7 @@ int check_onset_params(fluhip_ctx* ctx, int function, int64_t filterSize, int64_
   if (filterSize < 1 || filterSize > kOnsetMaxFilter || (filterSize % 2) == 0)
     return fail(ctx, "filterSize must be odd and in [1, 101]");
   if (frameDelta < 0 || frameDelta > kOnsetMaxDelta) return fail(ctx, "frameDelta must be in [0, 8192]");
-  if (win < 1 || hop < 1) return fail(ctx, "fftSettings: window and hop sizes must be positive");
-  if (fft < 4 || (fft & (fft - 1)) || fft < win || !stft_supported(win, fft))
-    return fail(ctx, "fftSettings: fft size must be a power of two >= window size, from 4 to 65536");
-  return FLUHIP_OK;
+  return check_fft_settings(ctx, win, fft, hop);
 }
 
 int check_slice_params(fluhip_ctx* ctx, double threshold, int64_t minSlice)
@@ -89,24 +60,14 @@ int check_onset_range(fluhip_ctx* ctx, int64_t n, int64_t base, int64_t T, int64
   return FLUHIP_OK;
 }
 
-int onset_stft(const OnsetRun& r, int64_t nb, int64_t b0, int64_t f0, int64_t rows, int64_t extra, double* spec,
-               const double* wtab, const double* ttab)
+// the spectra of frames f0 .. f0 + rows - 1 of buffers b0 .. b0 + nb - 1, each window `extra` samples on
+int onset_stft(const OnsetRun& r, const StftSetup& st, int64_t nb, int64_t b0, int64_t f0, int64_t rows, int64_t extra,
+               double* spec)
 {
-  fluhip_ctx* ctx = r.ctx;
-  const int64_t F = r.fft / 2 + 1;
-  StftArgs sa;
-  sa.audio = r.a32 ? r.a32 + b0 * r.stride : nullptr;
-  sa.audio64 = r.a64 ? r.a64 + b0 * r.stride : nullptr;
-  sa.n = r.n; sa.audioStride = r.stride;
-  sa.win = (int) r.win; sa.fft = (int) r.fft; sa.hop = (int) r.hop; sa.T = (int) rows; sa.F = (int) F; sa.B = (int) nb;
-  sa.window = wtab; sa.twiddle = ttab;
-  sa.mag = nullptr; sa.magStride = 0; sa.ldMag = 0;
-  sa.spec = spec; sa.specStride = rows * F * 2;
-  sa.frameOffset = (int) (r.win / 2 + r.base + f0 * r.hop + extra); // the kernels place frame t at t hop - win / 2 + frameOffset
-  sa.bigScratch = big_fft_scratch(ctx, r.win, r.fft, nb * rows);
-  if (stft_needs_scratch(r.win, r.fft) && !sa.bigScratch) return FLUHIP_ERROR;
-  launch_stft(sa, ctx->stream);
-  return FLUHIP_OK;
+  StftArgs sa = st.args(r.a32 ? r.a32 + b0 * r.stride : nullptr, r.a64 ? r.a64 + b0 * r.stride : nullptr, r.n, r.stride, nb,
+                        rows, r.base + f0 * r.hop + extra);
+  sa.spec = spec; sa.specStride = rows * st.F * 2;
+  return st.launch(r.ctx, sa);
 }
 
 // raw [nb][T] (device): OnsetDetectionFunctions::processFrame's function value of every frame
@@ -116,19 +77,13 @@ int onset_raw_dev(const OnsetRun& r, int64_t nb, double* raw)
   hipStream_t s = ctx->stream;
   const OnsetPlan plan = onset_plan(r.fft, r.win, r.function, r.frameDelta);
   const int64_t F = r.fft / 2 + 1, T = r.T;
-  const double *wtab = nullptr, *ttab = nullptr;
-  int rc = get_window(ctx, r.win, r.fft, FLUHIP_WINDOW_HANN, &wtab);
+  StftSetup st;
+  int rc = stft_setup(ctx, r.win, r.fft, r.hop, &st);
   if (rc) return rc;
-  if ((rc = get_twiddle(ctx, r.fft, &ttab))) return rc;
   if (plan.form == kOnsetFormOnChip)
   {
     // one launch over all buffers, no workspace: the spectra stay in the LDS (kernels_stft2.hip, onset_fused_kernel)
-    StftArgs sa;
-    sa.audio = r.a32; sa.audio64 = r.a64; sa.n = r.n; sa.audioStride = r.stride;
-    sa.win = (int) r.win; sa.fft = (int) r.fft; sa.hop = (int) r.hop; sa.T = (int) T; sa.F = (int) F;
-    sa.window = wtab; sa.twiddle = ttab;
-    sa.mag = nullptr; sa.magStride = 0; sa.ldMag = 0; sa.spec = nullptr; sa.specStride = 0;
-    sa.frameOffset = (int) (r.win / 2 + r.base);
+    StftArgs sa = st.args(r.a32, r.a64, r.n, r.stride, nb, T, r.base);
     OnsetFusedArgs o;
     o.function = r.function; o.history = plan.history;
     o.delta = plan.transforms == 2 ? (int) r.frameDelta : 0;
@@ -153,8 +108,8 @@ int onset_raw_dev(const OnsetRun& r, int64_t nb, double* raw)
   const int64_t run = whole ? T : rowsCap - plan.history;
   const int64_t rowsMax = whole ? T : rowsCap;
   DevBuf spec, spec2;
-  OALLOC(ctx, spec, (size_t) (per * rowsMax * F * 2) * sizeof(double), false);
-  if (plan.transforms == 2) OALLOC(ctx, spec2, (size_t) (per * rowsMax * F * 2) * sizeof(double), false);
+  DEV_ALLOC(ctx, "onset", spec, (size_t) (per * rowsMax * F * 2) * sizeof(double), false);
+  if (plan.transforms == 2) DEV_ALLOC(ctx, "onset", spec2, (size_t) (per * rowsMax * F * 2) * sizeof(double), false);
   for (int64_t b0 = 0; b0 < nb; b0 += per)
   {
     const int64_t cb = std::min(per, nb - b0);
@@ -163,8 +118,8 @@ int onset_raw_dev(const OnsetRun& r, int64_t nb, double* raw)
       const int64_t nt = std::min(run, T - t0);
       const int64_t f0 = std::max<int64_t>(0, t0 - plan.history);
       const int64_t rows = t0 + nt - f0;
-      if ((rc = onset_stft(r, cb, b0, f0, rows, 0, spec.as<double>(), wtab, ttab))) return rc;
-      if (plan.transforms == 2 && (rc = onset_stft(r, cb, b0, f0, rows, r.frameDelta, spec2.as<double>(), wtab, ttab))) return rc;
+      if ((rc = onset_stft(r, st, cb, b0, f0, rows, 0, spec.as<double>()))) return rc;
+      if (plan.transforms == 2 && (rc = onset_stft(r, st, cb, b0, f0, rows, r.frameDelta, spec2.as<double>()))) return rc;
       OnsetReduceArgs a;
       a.spec = spec.as<double>(); a.spec2 = plan.transforms == 2 ? spec2.as<double>() : nullptr;
       a.specStride = rows * F * 2;
@@ -197,13 +152,13 @@ int onset_f64_impl(fluhip_ctx* ctx, const double* signal, int64_t count, int64_t
   // buffers per round: the signals of a round stay below 1 GiB on the device
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(count, kSpecCapDoubles / np));
   DevBuf dSig, dRaw, dFilt, dDet, dCnt;
-  OALLOC(ctx, dSig, (size_t) (chunk * np) * sizeof(double), true); // (only the first n samples of a row are ever written)
-  OALLOC(ctx, dRaw, (size_t) (chunk * T) * sizeof(double), false);
-  OALLOC(ctx, dFilt, (size_t) (chunk * T) * sizeof(double), false);
+  DEV_ALLOC(ctx, "onset", dSig, (size_t) (chunk * np) * sizeof(double), true); // (only the first n samples of a row are ever written)
+  DEV_ALLOC(ctx, "onset", dRaw, (size_t) (chunk * T) * sizeof(double), false);
+  DEV_ALLOC(ctx, "onset", dFilt, (size_t) (chunk * T) * sizeof(double), false);
   if (slices)
   {
-    OALLOC(ctx, dDet, (size_t) (chunk * T), false);
-    OALLOC(ctx, dCnt, (size_t) chunk * sizeof(int64_t), false);
+    DEV_ALLOC(ctx, "onset", dDet, (size_t) (chunk * T), false);
+    DEV_ALLOC(ctx, "onset", dCnt, (size_t) chunk * sizeof(int64_t), false);
   }
   for (int64_t b0 = 0; b0 < count; b0 += chunk)
   {
@@ -254,8 +209,7 @@ int bufonsetslice_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int64
   // vectors of 64; a frame fires at every multiple of hop below that length and holds the win + d samples that END there
   const int64_t d = onset_uses_delta(function, frameDelta) ? frameDelta : 0;
   const int64_t latency = hop;
-  const int64_t padded = (n + latency + 63) / 64 * 64;
-  const int64_t T = (padded + hop - 1) / hop;
+  const int64_t T = slice_frames(n, hop, latency).T;
   if ((rc = check_onset_range(ctx, n, -(win + d), T, win, hop, d))) return rc;
   const int64_t lead = win + d, np = onset_padded_length(lead, n, T, hop, win + d);
   if (count > (INT64_MAX / 64) / std::max(T, np) / channels) return fail(ctx, "batch too large");
@@ -263,16 +217,16 @@ int bufonsetslice_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int64
   hipStream_t s = ctx->stream;
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(count, 2 * kSpecCapDoubles / (np * channels)));
   DevBuf dIn, dMono, dPad, dRaw, dFilt, dDet, dCnt;
-  OALLOC(ctx, dPad, (size_t) (chunk * np) * sizeof(float), true); // rows of [lead zeros][mono sum][zeros]; only the sum is written
+  DEV_ALLOC(ctx, "onset", dPad, (size_t) (chunk * np) * sizeof(float), true); // rows of [lead zeros][mono sum][zeros]; only the sum is written
   if (channels > 1)
   {
-    OALLOC(ctx, dIn, (size_t) (chunk * channels * n) * sizeof(float), false);
-    OALLOC(ctx, dMono, (size_t) (chunk * n) * sizeof(float), false);
+    DEV_ALLOC(ctx, "onset", dIn, (size_t) (chunk * channels * n) * sizeof(float), false);
+    DEV_ALLOC(ctx, "onset", dMono, (size_t) (chunk * n) * sizeof(float), false);
   }
-  OALLOC(ctx, dRaw, (size_t) (chunk * T) * sizeof(double), false);
-  OALLOC(ctx, dFilt, (size_t) (chunk * T) * sizeof(double), false);
-  OALLOC(ctx, dDet, (size_t) (chunk * T), false);
-  OALLOC(ctx, dCnt, (size_t) chunk * sizeof(int64_t), false);
+  DEV_ALLOC(ctx, "onset", dRaw, (size_t) (chunk * T) * sizeof(double), false);
+  DEV_ALLOC(ctx, "onset", dFilt, (size_t) (chunk * T) * sizeof(double), false);
+  DEV_ALLOC(ctx, "onset", dDet, (size_t) (chunk * T), false);
+  DEV_ALLOC(ctx, "onset", dCnt, (size_t) chunk * sizeof(int64_t), false);
   std::vector<unsigned char> det((size_t) (count * T));
   for (int64_t b0 = 0; b0 < count; b0 += chunk)
   {
@@ -295,24 +249,9 @@ int bufonsetslice_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int64
     HIPCHK(ctx, hipMemcpyAsync(det.data() + b0 * T, dDet.p, (size_t) (nb * T), hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
   }
-  // Slicing::process :709-722 + spikesToTimes: the detection of frame i stands at sample i hop of the padded signal; any
-  // detection inside the latency moves to the first sample, the rest lose the latency
   for (int64_t b = 0; b < count; b++)
-  {
-    const unsigned char* dd = det.data() + b * T;
-    int64_t* out = indices ? indices + b * capacity : nullptr;
-    int64_t cnt = 0;
-    auto put = [&](int64_t v) { if (cnt < capacity) out[cnt] = v; cnt++; };
-    if (dd[0] || (T > 1 && dd[1])) put(startFrame); // frames 0 and 1 stand at samples 0 and hop = latency
-    for (int64_t i = 2; i < T; i++)
-    {
-      const int64_t p = i * hop - latency;
-      if (p >= n) break;
-      if (dd[i]) put(p + startFrame);
-    }
-    if (cnt == 0) put(-1);
-    counts[b] = cnt;
-  }
+    counts[b] = detections_to_indices(det.data() + b * T, T, hop, latency, n, startFrame, indices ? indices + b * capacity : nullptr,
+                                      capacity);
   return FLUHIP_OK;
 }
 
@@ -329,15 +268,10 @@ int bufonsetfeature_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int
   // of hop samples and holds the win + d samples that END where that vector begins; the first latency / hop = 1 frame is
   // dropped
   const int64_t d = onset_uses_delta(function, frameDelta) ? frameDelta : 0;
-  const int64_t latency = hop, latencyHops = 1;
-  const int64_t userPad = paddingMode == 0 ? 0 : paddingMode == 1 ? win / 2 : win - hop;
   if (hop > INT32_MAX / 4 || n > INT32_MAX / 2) return fail(ctx, "signal too long");
-  int64_t paddedLength = n + latency + 2 * userPad;
-  if (paddingMode == 2) paddedLength = ((paddedLength + hop - 1) / hop) * hop;
-  if (paddedLength < win) return fail(ctx, "not enough frames");
-  const int64_t T = 1 + (paddedLength - win) / hop;
-  const int64_t keep = T - latencyHops;
-  if (keep < 1) return fail(ctx, "not enough frames");
+  const ControlFrames g = control_frames(n, win, hop, paddingMode, hop);
+  const int64_t userPad = g.userPad, T = g.T, latencyHops = g.latencyHops, keep = g.keep;
+  if (g.paddedLength < win || keep < 1) return fail(ctx, "not enough frames");
   if ((rc = check_onset_range(ctx, n, -(win + d + userPad), T, win, hop, d))) return rc;
   const int64_t lead = win + d + userPad, np = onset_padded_length(lead, n, T, hop, win + d);
   if (count > (INT64_MAX / 64) / std::max(T, np)) return fail(ctx, "batch too large");
@@ -347,10 +281,10 @@ int bufonsetfeature_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int
   hipStream_t s = ctx->stream;
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(count, 2 * kSpecCapDoubles / np));
   DevBuf dPad, dRaw, dFilt, dOut;
-  OALLOC(ctx, dPad, (size_t) (chunk * np) * sizeof(float), true); // rows of [lead zeros][input][zeros]; only the input is written
-  OALLOC(ctx, dRaw, (size_t) (chunk * T) * sizeof(double), false);
-  OALLOC(ctx, dFilt, (size_t) (chunk * T) * sizeof(double), false);
-  OALLOC(ctx, dOut, (size_t) (chunk * keep) * sizeof(float), false);
+  DEV_ALLOC(ctx, "onset", dPad, (size_t) (chunk * np) * sizeof(float), true); // rows of [lead zeros][input][zeros]; only the input is written
+  DEV_ALLOC(ctx, "onset", dRaw, (size_t) (chunk * T) * sizeof(double), false);
+  DEV_ALLOC(ctx, "onset", dFilt, (size_t) (chunk * T) * sizeof(double), false);
+  DEV_ALLOC(ctx, "onset", dOut, (size_t) (chunk * keep) * sizeof(float), false);
   for (int64_t b0 = 0; b0 < count; b0 += chunk)
   {
     const int64_t nb = std::min(chunk, count - b0);
@@ -389,7 +323,7 @@ int fluhip_onset_curve_f64(fluhip_ctx* ctx, const double* signal, int64_t count,
                            int64_t fft, int64_t hop, int function, int64_t filter_size, int64_t frame_delta, double* raw,
                            double* filtered)
 {
-  return guarded_onset(ctx, [&] {
+  return guarded(ctx, [&] {
     return onset_f64_impl(ctx, signal, count, n, ld, T, win, fft, hop, function, filter_size, frame_delta, false, 0.0, 0, raw,
                           filtered, nullptr, nullptr);
   });
@@ -399,7 +333,7 @@ int fluhip_onset_slices_f64(fluhip_ctx* ctx, const double* signal, int64_t count
                             int64_t fft, int64_t hop, int function, int64_t filter_size, int64_t frame_delta, double threshold,
                             int64_t min_slice, unsigned char* det, int64_t* counts, double* filtered)
 {
-  return guarded_onset(ctx, [&] {
+  return guarded(ctx, [&] {
     return onset_f64_impl(ctx, signal, count, n, ld, T, win, fft, hop, function, filter_size, frame_delta, true, threshold,
                           min_slice, nullptr, filtered, det, counts);
   });
@@ -410,7 +344,7 @@ int fluhip_bufonsetslice_f32(fluhip_ctx* ctx, const float* audio, int64_t count,
                              int64_t frame_delta, int64_t win, int64_t fft, int64_t hop, int64_t* indices, int64_t capacity,
                              int64_t* counts)
 {
-  return guarded_onset(ctx, [&] {
+  return guarded(ctx, [&] {
     return bufonsetslice_impl(ctx, audio, count, channels, n, start_frame, function, threshold, min_slice, filter_size,
                               frame_delta, win, fft, hop, indices, capacity, counts);
   });
@@ -420,7 +354,7 @@ int fluhip_bufonsetfeature_f32(fluhip_ctx* ctx, const float* audio, int64_t coun
                                int64_t filter_size, int64_t frame_delta, int64_t win, int64_t fft, int64_t hop,
                                int padding_mode, float* out, int64_t* frames_out)
 {
-  return guarded_onset(ctx, [&] {
+  return guarded(ctx, [&] {
     return bufonsetfeature_impl(ctx, audio, count, n, function, filter_size, frame_delta, win, fft, hop, padding_mode, out,
                                 frames_out);
   });

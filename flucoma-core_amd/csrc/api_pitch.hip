@@ -14,33 +14,7 @@
 #include "fluhip_env.h"
 #include "fluhip_pitch.h"
 
-#include <new>
-
 namespace {
-
-template <typename Fn> int guarded_pitch(fluhip_ctx* ctx, Fn&& fn)
-{
-  if (!ctx) return FLUHIP_ERROR;
-  try
-  {
-    return fn();
-  }
-  catch (const std::bad_alloc&)
-  {
-    return fail_oom(ctx, "host allocation failed");
-  }
-  catch (...)
-  {
-    return fail(ctx, "internal error");
-  }
-}
-
-#define PALLOC(ctx, buf, bytes, zero)                                                              \
-  do                                                                                               \
-  {                                                                                                \
-    hipError_t e__ = (buf).alloc((bytes), (zero), (ctx)->stream);                                  \
-    if (e__ != hipSuccess) return fail_hip((ctx), e__, "device allocation of the pitch workspace"); \
-  } while (0)
 
 constexpr int64_t kWorkCapDoubles = (int64_t) 1 << 27; // 1 GiB of workspace per round
 constexpr int64_t kRoundMaxFrames = (int64_t) 1 << 21; // (the GEMM's grid: frames / 64 workgroup rows)
@@ -102,22 +76,22 @@ int pitch_work_alloc(PitchWork& w, int64_t nfMax)
   {
     int rc = get_twiddle(ctx, w.fft, &w.ttab);
     if (rc) return rc;
-    PALLOC(ctx, w.sym, (size_t) (nfMax * w.fft) * sizeof(double), false);
-    PALLOC(ctx, w.spec, (size_t) (nfMax * w.F * 2) * sizeof(double), false);
-    PALLOC(ctx, w.curve, (size_t) (nfMax * w.F) * sizeof(double), false);
-    PALLOC(ctx, w.aux, (size_t) nfMax * sizeof(double), false);
-    PALLOC(ctx, w.ones, (size_t) w.fft * sizeof(double), false);
+    DEV_ALLOC(ctx, "pitch", w.sym, (size_t) (nfMax * w.fft) * sizeof(double), false);
+    DEV_ALLOC(ctx, "pitch", w.spec, (size_t) (nfMax * w.F * 2) * sizeof(double), false);
+    DEV_ALLOC(ctx, "pitch", w.curve, (size_t) (nfMax * w.F) * sizeof(double), false);
+    DEV_ALLOC(ctx, "pitch", w.aux, (size_t) nfMax * sizeof(double), false);
+    DEV_ALLOC(ctx, "pitch", w.ones, (size_t) w.fft * sizeof(double), false);
     launch_pitch_fill(w.ones.as<double>(), w.fft, 1.0, s);
   }
   else if (w.algorithm == kPitchCepstrum)
   {
-    PALLOC(ctx, w.lg, (size_t) (nfMax * w.F) * sizeof(double), false);
-    PALLOC(ctx, w.table, (size_t) (w.rows * w.F) * sizeof(double), false);
-    PALLOC(ctx, w.cep, (size_t) (nfMax * w.rows) * sizeof(double), false);
+    DEV_ALLOC(ctx, "pitch", w.lg, (size_t) (nfMax * w.F) * sizeof(double), false);
+    DEV_ALLOC(ctx, "pitch", w.table, (size_t) (w.rows * w.F) * sizeof(double), false);
+    DEV_ALLOC(ctx, "pitch", w.cep, (size_t) (nfMax * w.rows) * sizeof(double), false);
     launch_pitch_dct_table(w.table.as<double>(), w.F, w.lo, w.rows, s); // once per call
   }
   else if (w.algorithm == kPitchHPS && w.fullCurve)
-    PALLOC(ctx, w.curve, (size_t) (nfMax * w.F) * sizeof(double), false);
+    DEV_ALLOC(ctx, "pitch", w.curve, (size_t) (nfMax * w.F) * sizeof(double), false);
   HIPCHK(ctx, hipGetLastError());
   return FLUHIP_OK;
 }
@@ -153,16 +127,11 @@ int pitch_round(PitchWork& w, const PitchFrames& p, double* out)
   else if (w.algorithm == kPitchYinFFT)
   {
     launch_pitch_sym(p, w.sym.as<double>(), s);
-    StftArgs sa;
-    sa.audio = nullptr; sa.audio64 = w.sym.as<double>(); sa.n = p.nf * w.fft; sa.audioStride = sa.n;
-    sa.win = (int) w.fft; sa.fft = (int) w.fft; sa.hop = (int) w.fft; sa.T = (int) p.nf; sa.F = (int) w.F; sa.B = 1;
-    sa.window = w.ones.as<double>(); sa.twiddle = w.ttab;
-    sa.mag = nullptr; sa.magStride = 0; sa.ldMag = 0;
+    // the second transform: window = hop = fft over the rows of sym, a table of ones as the window
+    const StftSetup sym{w.fft, w.fft, w.fft, w.F, w.ones.as<double>(), w.ttab};
+    StftArgs sa = sym.args(nullptr, w.sym.as<double>(), p.nf * w.fft, p.nf * w.fft, 1, p.nf, 0);
     sa.spec = w.spec.as<double>(); sa.specStride = p.nf * w.F * 2;
-    sa.frameOffset = (int) (w.fft / 2); // frame t starts at sample t fft
-    sa.bigScratch = big_fft_scratch(ctx, w.fft, w.fft, p.nf);
-    if (stft_needs_scratch(w.fft, w.fft) && !sa.bigScratch) return FLUHIP_ERROR;
-    launch_stft(sa, s);
+    if (const int rc = sym.launch(ctx, sa)) return rc;
     launch_pitch_yin_norm(p, w.spec.as<double>(), w.curve.as<double>(), w.F, w.aux.as<double>(), s);
     launch_pitch_peak(kPitchYinFFT, w.curve.as<double>(), w.F, w.aux.as<double>(), p.nf, w.lo, w.hi, w.sampleRate, out, s);
   }
@@ -218,8 +187,8 @@ int pitch_frames_impl(fluhip_ctx* ctx, const double* mag, int64_t count, int64_t
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min(nfAll, kRoundMaxFrames), kWorkCapDoubles / per));
   if ((rc = pitch_work_alloc(w, chunk))) return rc;
   DevBuf dMag, dOut;
-  PALLOC(ctx, dMag, (size_t) (chunk * ld) * sizeof(double), false);
-  PALLOC(ctx, dOut, (size_t) (chunk * 2) * sizeof(double), false);
+  DEV_ALLOC(ctx, "pitch", dMag, (size_t) (chunk * ld) * sizeof(double), false);
+  DEV_ALLOC(ctx, "pitch", dOut, (size_t) (chunk * 2) * sizeof(double), false);
   for (int64_t f0 = 0; f0 < nfAll; f0 += chunk)
   {
     const int64_t nf = std::min(chunk, nfAll - f0);
@@ -248,11 +217,9 @@ int bufpitch_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n,
                   int paddingMode, int algorithm, double minFreq, double maxFreq, int unit, int select, double sampleRate,
                   float* out, int64_t* framesOut)
 {
-  if (win < 1 || hop < 1) return fail(ctx, "fftSettings: window and hop sizes must be positive");
-  if (fft < 4 || (fft & (fft - 1)) || fft < win || !stft_supported(win, fft))
-    return fail(ctx, "fftSettings: fft size must be a power of two >= window size, from 4 to 65536");
-  int rc = check_pitch_params(ctx, algorithm, minFreq, maxFreq, sampleRate, fft);
+  int rc = check_fft_settings(ctx, win, fft, hop);
   if (rc) return rc;
+  if ((rc = check_pitch_params(ctx, algorithm, minFreq, maxFreq, sampleRate, fft))) return rc;
   if (select < 1 || select > 3)
     return fail(ctx, select == 0 ? "select is empty: choose pitch (1), confidence (2) or both (3)" : "select must be in [1, 3]");
   if (unit < 0 || unit > 1) return fail(ctx, "unit must be 0 (Hz) or 1 (MIDI)");
@@ -264,11 +231,8 @@ int bufpitch_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n,
   // StreamingControl::process (cc/FluidNRTClientWrapper.hpp:564-579, 642-656): the input sits userPad into the padded
   // signal, the client's latency (= win, PitchClient.hpp:151) in front of it; analysis frame j holds the win samples from
   // j hop - win - userPad of the input on; the first latency / hop frames are dropped
-  const int64_t latencyHops = win / hop;
-  const int64_t userPad = paddingMode == 0 ? 0 : paddingMode == 1 ? win / 2 : win - hop;
-  int64_t paddedLength = n + win + 2 * userPad;
-  if (paddingMode == 2) paddedLength = ((paddedLength + hop - 1) / hop) * hop;
-  const int64_t T = 1 + (paddedLength - win) / hop - latencyHops;
+  const ControlFrames g = control_frames(n, win, hop, paddingMode, win);
+  const int64_t latencyHops = g.latencyHops, userPad = g.userPad, T = g.keep; // (only the kept frames are computed)
   if (T < 1) return fail(ctx, "not enough frames");
   if (T > INT32_MAX / 4 || T + latencyHops > (INT32_MAX / 2 - 2 * win - userPad) / hop) return fail(ctx, "signal too long");
   // rows of [lead zeros][input][zeros] so that every frame lies inside its row: frame j starts at sample j hop
@@ -281,9 +245,8 @@ int bufpitch_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n,
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const int64_t F = fft / 2 + 1, Fp = round_up(F, 32);
-  const double *wtab = nullptr, *ttab = nullptr;
-  if ((rc = get_window(ctx, win, fft, FLUHIP_WINDOW_HANN, &wtab))) return rc;
-  if ((rc = get_twiddle(ctx, fft, &ttab))) return rc;
+  StftSetup st;
+  if ((rc = stft_setup(ctx, win, fft, hop, &st))) return rc;
   PitchWork w;
   if ((rc = pitch_work_init(w, ctx, algorithm, F, minFreq, maxFreq, sampleRate, false))) return rc;
   // frames a round holds: whole buffers when one fits, else runs of one buffer's frames
@@ -298,10 +261,10 @@ int bufpitch_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n,
   const int64_t run = whole ? T : rowsCap;
   if ((rc = pitch_work_alloc(w, perB * run))) return rc;
   DevBuf dPad, dMag, dRes, dOut;
-  PALLOC(ctx, dPad, (size_t) (perB * np) * sizeof(float), true); // only the input is ever written
-  if (!chip) PALLOC(ctx, dMag, (size_t) (perB * run * Fp) * sizeof(double), false);
-  PALLOC(ctx, dRes, (size_t) (perB * T * 2) * sizeof(double), false);
-  PALLOC(ctx, dOut, (size_t) (perB * nsel * T) * sizeof(float), false);
+  DEV_ALLOC(ctx, "pitch", dPad, (size_t) (perB * np) * sizeof(float), true); // only the input is ever written
+  if (!chip) DEV_ALLOC(ctx, "pitch", dMag, (size_t) (perB * run * Fp) * sizeof(double), false);
+  DEV_ALLOC(ctx, "pitch", dRes, (size_t) (perB * T * 2) * sizeof(double), false);
+  DEV_ALLOC(ctx, "pitch", dOut, (size_t) (perB * nsel * T) * sizeof(float), false);
   for (int64_t b0 = 0; b0 < count; b0 += perB)
   {
     const int64_t nb = std::min(perB, count - b0);
@@ -310,27 +273,16 @@ int bufpitch_impl(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n,
     for (int64_t t0 = 0; t0 < T; t0 += run)
     {
       const int64_t nt = std::min(run, T - t0);
-      StftArgs sa;
-      sa.audio = dPad.as<float>(); sa.audio64 = nullptr; sa.n = np; sa.audioStride = np;
-      sa.win = (int) win; sa.fft = (int) fft; sa.hop = (int) hop; sa.T = (int) nt; sa.F = (int) F; sa.B = (int) nb;
-      sa.window = wtab; sa.twiddle = ttab;
+      StftArgs sa = st.args(dPad.as<float>(), nullptr, np, np, nb, nt, (latencyHops + t0) * hop); // (analysis frame j starts at j hop of a row)
       sa.mag = chip ? nullptr : dMag.as<double>(); sa.magStride = nt * Fp; sa.ldMag = Fp;
-      sa.spec = nullptr; sa.specStride = 0;
-      sa.frameOffset = (int) (win / 2 + (latencyHops + t0) * hop); // the kernels place frame t at t hop - win / 2 + frameOffset
       // (one buffer per round when its frames come in runs: the results of run t0 go behind those before it)
       double* res = dRes.as<double>() + (whole ? 0 : t0 * 2);
       if (chip)
       {
-        sa.bigScratch = nullptr;
         if ((rc = pitch_round_fused(w, sa, res))) return rc;
         continue;
       }
-      sa.bigScratch = big_fft_scratch(ctx, win, fft, nb * nt);
-      if (stft_needs_scratch(win, fft) && !sa.bigScratch) return FLUHIP_ERROR;
-      {
-        ProfScope ps(ctx, 0);
-        launch_stft(sa, s);
-      }
+      if ((rc = st.launch(ctx, sa, 0))) return rc;
       HIPCHK(ctx, hipGetLastError());
       PitchFrames p{dMag.as<double>(), nt * Fp, Fp, nt, nb * nt, (int) F};
       if ((rc = pitch_round(w, p, res))) return rc;
@@ -367,7 +319,7 @@ int fluhip_debug_pitch_plan(fluhip_ctx* ctx, int64_t fft, int64_t win, int algor
 int fluhip_pitch_frames_f64(fluhip_ctx* ctx, const double* mag, int64_t count, int64_t T, int64_t F, int64_t ld, int algorithm,
                             double min_freq, double max_freq, double sample_rate, double* out)
 {
-  return guarded_pitch(ctx, [&] {
+  return guarded(ctx, [&] {
     if (!out) return fail(ctx, "null buffer");
     return pitch_frames_impl(ctx, mag, count, T, F, ld, algorithm, min_freq, max_freq, sample_rate, out, nullptr);
   });
@@ -376,7 +328,7 @@ int fluhip_pitch_frames_f64(fluhip_ctx* ctx, const double* mag, int64_t count, i
 int fluhip_debug_pitch_curve_f64(fluhip_ctx* ctx, const double* mag, int64_t count, int64_t T, int64_t F, int64_t ld,
                                  int algorithm, double min_freq, double max_freq, double sample_rate, double* curve)
 {
-  return guarded_pitch(ctx, [&] {
+  return guarded(ctx, [&] {
     if (!curve) return fail(ctx, "null buffer");
     return pitch_frames_impl(ctx, mag, count, T, F, ld, algorithm, min_freq, max_freq, sample_rate, nullptr, curve);
   });
@@ -386,7 +338,7 @@ int fluhip_bufpitch_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int6
                         int padding_mode, int algorithm, double min_freq, double max_freq, int unit, int select,
                         double sample_rate, float* out, int64_t* frames_out)
 {
-  return guarded_pitch(ctx, [&] {
+  return guarded(ctx, [&] {
     return bufpitch_impl(ctx, audio, count, n, win, fft, hop, padding_mode, algorithm, min_freq, max_freq, unit, select,
                          sample_rate, out, frames_out);
   });

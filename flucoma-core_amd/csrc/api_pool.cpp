@@ -8,6 +8,7 @@
 // one host process owns all devices ("D2H per GPU is equally valid").  Built on the public corpus entry
 // points only, so it is also a usage example of them.  Plain C++17, no HIP in this file.
 #include "../../include/flucoma_hip.h"
+#include "client_frames.h"
 #include "fluhip_env.h"
 
 #include <algorithm>
@@ -417,10 +418,7 @@ static int pool_features(fluhip_pool* p, bool mfcc, const float* audio, int64_t 
   if (padding_mode < 0 || padding_mode > 2) { p->err = "padding mode must be 0 (None), 1 (Default) or 2 (Full)"; return FLUHIP_ERROR; }
   const int world = (int) p->ctx.size();
   // frames per slice, as the single-device entry points count them (include/flucoma_hip.h)
-  const int64_t userPad = padding_mode == 0 ? 0 : padding_mode == 1 ? win / 2 : win - hop;
-  int64_t padded = n + win + 2 * userPad;
-  if (padding_mode == 2) padded = ((padded + hop - 1) / hop) * hop;
-  const int64_t T = 1 + (padded - win) / hop - win / hop;
+  const int64_t T = fluhip::control_frames(n, win, hop, padding_mode, win).keep;
   if (T < 1) { p->err = "not enough frames"; return FLUHIP_ERROR; }
   const int64_t nOut = mfcc ? n_coefs : n_bands;
   std::vector<int> rcs((size_t) world, FLUHIP_OK);

@@ -37,25 +37,26 @@ inline void request_dynamic_lds(Kern kern, size_t bytes)
 // stays zero (zero rows/cols contribute exactly 0 to every contraction).
 // ---------------------------------------------------------------------------------------
 
+// Every field a launch may leave out has its neutral value here: a site names only what it uses.
 struct StftArgs
 {
-  const float* audio;   // [B][n]  (or nullptr when audio64 is used)
-  const double* audio64; // [B][n] f64 input variant
-  int64_t n;            // samples per buffer
-  int64_t audioStride;  // elements between buffers
-  int win, fft, hop;
-  int T, F;             // frames per buffer, bins
-  int B;
-  const double* window; // [win]
-  const double* twiddle; // [fft/2] interleaved (cos, sin) of e^{-2 pi i j / fft}
-  double* mag;          // [B][Tp][Fp] or nullptr
-  int64_t magStride;    // per buffer
-  int64_t ldMag;        // Fp
-  double* spec;         // [B][T][F] interleaved complex, or nullptr
-  int64_t specStride;
+  const float* audio = nullptr;    // [B][n]  (or nullptr when audio64 is used)
+  const double* audio64 = nullptr; // [B][n] f64 input variant
+  int64_t n = 0;            // samples per buffer
+  int64_t audioStride = 0;  // elements between buffers
+  int win = 0, fft = 0, hop = 0;
+  int T = 0, F = 0;         // frames per buffer, bins
+  int B = 1;
+  const double* window = nullptr;  // [win]
+  const double* twiddle = nullptr; // [fft/2] interleaved (cos, sin) of e^{-2 pi i j / fft}
+  double* mag = nullptr;    // [B][Tp][Fp] or nullptr
+  int64_t magStride = 0;    // per buffer
+  int64_t ldMag = 0;        // Fp
+  double* spec = nullptr;   // [B][T][F] interleaved complex, or nullptr
+  int64_t specStride = 0;
   double* bigScratch = nullptr; // big_fft_scratch_bytes() of workspace, needed when stft_needs_scratch(win, fft)
-  int frameOffset;      // extra sample offset of frame 0 (0 for STFT::process; the buffered feature
-                        // clients start (win/hop)*hop - win earlier when hop does not divide win)
+  int frameOffset = 0;      // frame t starts at sample t hop - win / 2 + frameOffset of its buffer: 0 for STFT::process'
+                            // centred frames (api_internal.h StftSetup::args is where the clients' frame positions become this)
   // ragged corpora (block form only): samples of every buffer (device, [B]); n / T are then those of the longest one
   // and frames past a buffer's own (n_b + hop) / hop are left zero
   const int64_t* nTab = nullptr;
@@ -391,22 +392,22 @@ bool stft_features_fits(int fft, int nBands, int nDct);
 // resynthesis: masked inverse STFT of component k with overlap-add
 struct ResynthArgs
 {
-  const double* spec;   // [T][F] interleaved complex
-  const double* Wf;     // [Fp][Kp]
-  const double* H1;     // [Tp][Kp]
-  const double* Vhat;   // [T][ldV]
-  int64_t ldV;
-  int Kp, k;
-  int win, fft, hop, T, F;
-  const double* window;
-  const double* twiddle;
-  double* frames;       // scratch [T][win] windowed, scaled inverse frames
-  double* out;          // [n] f64 overlap-added, normalised, trimmed
-  float* out32;         // [n] or nullptr
-  int64_t n;
+  const double* spec = nullptr; // [T][F] interleaved complex
+  const double* Wf = nullptr;   // [Fp][Kp]
+  const double* H1 = nullptr;   // [Tp][Kp]
+  const double* Vhat = nullptr; // [T][ldV]
+  int64_t ldV = 0;
+  int Kp = 0, k = 0;
+  int win = 0, fft = 0, hop = 0, T = 0, F = 0;
+  const double* window = nullptr;
+  const double* twiddle = nullptr;
+  double* frames = nullptr;     // scratch [T][win] windowed, scaled inverse frames
+  double* out = nullptr;        // [n] f64 overlap-added, normalised, trimmed
+  float* out32 = nullptr;       // [n] or nullptr
+  int64_t n = 0;
   int64_t outStride = 0; // samples between the components' outputs (0: n)
-  int64_t trim;         // leading samples dropped: win/2 for ISTFT::process, `padding` for BufSTFT
-  int nComp = 1;        // components k .. k + nComp - 1 in one launch: frames [nComp][T][win], out / out32 [nComp][n]
+  int64_t trim = 0;      // leading samples dropped: win/2 for ISTFT::process, `padding` for BufSTFT
+  int nComp = 1;         // components k .. k + nComp - 1 in one launch: frames [nComp][T][win], out / out32 [nComp][n]
   double* bigScratch = nullptr; // set (big_fft_scratch_bytes(fft, T)) when stft_needs_scratch(win, fft): global-memory passes
 };
 // Wf == nullptr: no ratio mask (plain inverse STFT of `spec`)
