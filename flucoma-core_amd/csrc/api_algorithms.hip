@@ -67,6 +67,74 @@ int fluhip_stft_f32(fluhip_ctx* ctx, const float* audio, int64_t n, int64_t stri
   return stft_common(ctx, audio, nullptr, n, stride, win, fft, hop, window_type, spec, mag, frames_out);
 }
 
+// Diagnostic: the inverse transform the resynthesising clients share (kernels_istft.hip), on the caller's own doubles and
+// with a double output -- RatioMask::process + ISTFT::process (alg/RatioMask.hpp:33-57, alg/STFT.hpp:178-199) with the trim
+// as a parameter.  The tables, the launch and the form taken (on-chip or global-memory passes) are the clients':
+// stft_setup, StftSetup::resynth, StftSetup::launch.
+static int debug_resynth_impl(fluhip_ctx* ctx, const double* spec, int64_t T, int64_t win, int64_t fft, int64_t hop, int64_t n,
+                              int64_t trim, const double* W, const double* H, int64_t K, double* out)
+{
+  const char* me = "fluhip_debug_resynth_f64: ";
+  if (!spec || !out) return fail(ctx, std::string(me) + "null spec or out");
+  if (win < 1 || hop < 1 || hop > 2000000000LL) return fail(ctx, std::string(me) + "win and hop must be positive (hop at most 2000000000)");
+  if (fft < 4 || (fft & (fft - 1)) || fft < win || !stft_supported(win, fft))
+    return fail(ctx, std::string(me) + "fft must be a power of two >= win, from 4 to 65536");
+  if (T < 1 || T > 2000000000LL / 16) return fail(ctx, std::string(me) + "T must be from 1 to 125000000");
+  if (n < 1 || n > 2000000000LL) return fail(ctx, std::string(me) + "n must be from 1 to 2000000000");
+  if (trim < 0 || trim > 2000000000LL) return fail(ctx, std::string(me) + "trim must be from 0 to 2000000000");
+  if ((W == nullptr) != (H == nullptr)) return fail(ctx, std::string(me) + "W and H must be given together");
+  const bool masked = W != nullptr;
+  if (masked && K < 1) return fail(ctx, std::string(me) + "K must be >= 1 with factors");
+  const int64_t F = fft / 2 + 1, Kout = masked ? K : 1;
+  if (masked)
+    if (int rcr = check_rank(ctx, T, F, K)) return rcr;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  StftSetup st;
+  int rc = stft_setup(ctx, win, fft, hop, &st);
+  if (rc) return rc;
+  DevBuf dspec, frames, dout, wsrc, hsrc, Wf, H1, vhat;
+  DEV_ALLOC(ctx, "spectrum", dspec, (size_t) T * F * 2 * sizeof(double), false);
+  HIPCHK(ctx, hipMemcpyAsync(dspec.p, spec, (size_t) T * F * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+  // every component in one launch, unless their frames pass 1 GiB (the clients' rule: nmffilter_impl, fluhip_corpus_resynth_dev)
+  const int64_t compsPerLaunch = std::max<int64_t>(1, std::min<int64_t>(Kout, ((int64_t) 1 << 30) / (T * win * 8)));
+  DEV_ALLOC(ctx, "frame", frames, (size_t) compsPerLaunch * T * win * sizeof(double), false);
+  DEV_ALLOC(ctx, "output", dout, (size_t) Kout * n * sizeof(double), false);
+  ResynthArgs ra = st.resynth(dspec.as<double>(), T, frames.as<double>(), n, trim);
+  ra.outStride = n;
+  if (masked)
+  {
+    const int64_t Kp = padded_rank(K), Fp = round_up(F, 32), Tp = round_up(T, 32);
+    DEV_ALLOC(ctx, "factor", wsrc, (size_t) K * F * sizeof(double), false);
+    DEV_ALLOC(ctx, "factor", hsrc, (size_t) T * K * sizeof(double), false);
+    DEV_ALLOC(ctx, "factor", Wf, (size_t) Fp * Kp * sizeof(double), true);
+    DEV_ALLOC(ctx, "factor", H1, (size_t) Tp * Kp * sizeof(double), true);
+    DEV_ALLOC(ctx, "estimate", vhat, (size_t) T * F * sizeof(double), false);
+    HIPCHK(ctx, hipMemcpyAsync(wsrc.p, W, (size_t) K * F * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(hsrc.p, H, (size_t) T * K * sizeof(double), hipMemcpyHostToDevice, s));
+    launch_scatter_factor(wsrc.as<double>(), 0, Wf.as<double>(), 0, (int) F, (int) K, (int) Kp, 1, true, s);
+    launch_scatter_factor(hsrc.as<double>(), 0, H1.as<double>(), 0, (int) T, (int) K, (int) Kp, 1, false, s);
+    launch_vhat(Wf.as<double>(), 0, H1.as<double>(), 0, vhat.as<double>(), F, 0, (int) T, (int) F, (int) Kp, 1, s);
+    ra.Wf = Wf.as<double>(); ra.H1 = H1.as<double>(); ra.Vhat = vhat.as<double>(); ra.ldV = F; ra.Kp = (int) Kp;
+  }
+  for (int64_t k = 0; k < Kout; k += compsPerLaunch)
+  {
+    ra.k = (int) k;
+    ra.nComp = (int) std::min(compsPerLaunch, Kout - k);
+    ra.out = dout.as<double>() + k * n;
+    if ((rc = st.launch(ctx, ra))) return rc;
+  }
+  HIPCHK(ctx, hipGetLastError());
+  const size_t nbytes = (size_t) Kout * n * sizeof(double);
+  return copy_to_host(ctx, out, nbytes, dout.p, nbytes, nbytes, 1, s);
+}
+
+int fluhip_debug_resynth_f64(fluhip_ctx* ctx, const double* spec, int64_t T, int64_t win, int64_t fft, int64_t hop, int64_t n,
+                             int64_t trim, const double* W, const double* H, int64_t K, double* out)
+{
+  return guarded(ctx, [&] { return debug_resynth_impl(ctx, spec, T, win, fft, hop, n, trim, W, H, K, out); });
+}
+
 // ---- two-stride views at the algorithm boundary (data/FluidTensor_Support.hpp:260-420, util/FluidEigenMappings.hpp:35-225)
 } // extern "C" (the helpers below are C++)
 namespace {

@@ -74,7 +74,7 @@ EXPORTS = [
     "fluhip_debug_onset_plan",
     "fluhip_hpss_planes_f64", "fluhip_bufhpss_f32", "fluhip_debug_hpss_plan",
     "fluhip_pitch_frames_f64", "fluhip_debug_pitch_curve_f64", "fluhip_bufpitch_f32", "fluhip_debug_pitch_plan",
-    "fluhip_debug_features_plan",
+    "fluhip_debug_features_plan", "fluhip_debug_resynth_f64",
 ]
 
 
@@ -110,6 +110,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.fluhip_stft_num_frames.restype = _i64
     L.fluhip_stft_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, _dp, _dp, _ip]
     L.fluhip_stft_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, _dp, _dp, _ip]
+    L.fluhip_debug_resynth_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _dp, _dp, _i64, _dp]
     L.fluhip_nmf_process_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int,
                                          ctypes.c_int, _i64, _dp, _dp, _dp, _dp, _dp, PROGRESS_FN, _vp]
     _mv = ctypes.POINTER(MatrixView)
@@ -312,6 +313,28 @@ class Context:
         assert Tout.value == T
         cs = spec[..., 0] + 1j * spec[..., 1] if want_spec else None
         return cs, mag
+
+    def resynth_f64(self, spec, win, fft, hop, n, trim, W=None, H=None, out=None):
+        """fluhip_debug_resynth_f64: the clients' inverse transform on doubles.  spec [T,F] complex (or [T,F,2] doubles);
+        W [K,F] and H [T,K] (both or neither) for the ratio-masked components.  Returns [n] without factors, [K,n] with them;
+        `out` (a C-contiguous float64 array of that shape) is filled in place when given."""
+        spec = np.asarray(spec)
+        if np.iscomplexobj(spec):
+            spec = np.ascontiguousarray(spec, dtype=np.complex128).view(np.float64).reshape(spec.shape + (2,))
+        spec = np.ascontiguousarray(spec, dtype=np.float64)
+        T = spec.shape[0]
+        assert spec.shape == (T, fft // 2 + 1, 2)
+        Wc = None if W is None else np.ascontiguousarray(W, dtype=np.float64)
+        Hc = None if H is None else np.ascontiguousarray(H, dtype=np.float64)
+        K = 0 if Wc is None else Wc.shape[0]
+        assert Wc is None or Wc.shape == (K, fft // 2 + 1)
+        assert Hc is None or Wc is None or Hc.shape == (T, K)
+        shape = (n,) if Wc is None and Hc is None else (max(K, 1), n)
+        if out is None:
+            out = np.empty(shape)
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == shape
+        self._check(self.lib.fluhip_debug_resynth_f64(self.h, _d(spec), T, win, fft, hop, n, trim, _d(Wc), _d(Hc), K, _d(out)))
+        return out
 
     # ---- algorithm::NMF -----------------------------------------------------------------
     def nmf_process(self, X, K, iters, updateW=True, updateH=True, seed=42, W0=None, H0=None,

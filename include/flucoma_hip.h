@@ -37,7 +37,7 @@ extern "C" {
  * fluhip_bufnoveltyslice_f32, fluhip_bufnoveltyfeature_f32, fluhip_debug_novelty_plan, fluhip_onset_curve_f64,
  * fluhip_onset_slices_f64, fluhip_bufonsetslice_f32, fluhip_bufonsetfeature_f32, fluhip_debug_onset_plan,
  * fluhip_debug_features_plan, fluhip_hpss_planes_f64, fluhip_bufhpss_f32, fluhip_debug_hpss_plan, fluhip_pitch_frames_f64,
- * fluhip_debug_pitch_curve_f64, fluhip_bufpitch_f32, fluhip_debug_pitch_plan. */
+ * fluhip_debug_pitch_curve_f64, fluhip_bufpitch_f32, fluhip_debug_pitch_plan, fluhip_debug_resynth_f64. */
 #define FLUHIP_ABI_VERSION 5
 
 /* clients/common/Result.hpp:24  enum class Status { kOk, kWarning, kError, kCancelled } */
@@ -119,6 +119,18 @@ int fluhip_stft_f64(fluhip_ctx* ctx, const double* audio, int64_t n, int64_t str
 int fluhip_stft_f32(fluhip_ctx* ctx, const float* audio, int64_t n, int64_t stride, int64_t win,
                     int64_t fft, int64_t hop, int window_type, double* spec, double* mag,
                     int64_t* frames_out);
+
+/* Diagnostic: the inverse every resynthesising client runs (BufNMF, NMFFilter, BufHPSS, BufSTFT, Griffin-Lim), on the caller's
+ * own doubles and with a double result -- RatioMask::process + ISTFT::process (algorithms/public/RatioMask.hpp:33-57,
+ * STFT.hpp:178-199) through the same tables, kernels and choice of form (on-chip, or the global-memory passes above fft 8192).
+ * spec: T x F interleaved (re,im) doubles; the imaginary parts of DC and Nyquist are ignored.  win, fft, hop as for the
+ * forward transform; out sample i is position i + trim of the overlap-added frames (frame t at [t hop, t hop + win)) divided
+ * by max(overlap-added window^2, eps): trim = win / 2 is ISTFT::process.  Positions no frame covers are 0.
+ * W (K x F) and H (T x K), both NULL or both given: with them component k is the inverse of spec * min(H[t][k] W[k][f] *
+ * (1 / max((H W)[t][f], eps)), 1), all K in one launch; out: max(K, 1) x n doubles (K is ignored without factors).
+ * Bad arguments: FLUHIP_ERROR with a message that names them, out untouched. */
+int fluhip_debug_resynth_f64(fluhip_ctx* ctx, const double* spec, int64_t T, int64_t win, int64_t fft, int64_t hop, int64_t n,
+                             int64_t trim, const double* W, const double* H, int64_t K, double* out);
 
 /* ---- algorithm::NMF ------------------------------------------------------------------- */
 /* Replaces NMF::process(X, W1, H1, V1, rank, nIterations, updateW, updateH, randomSeed, W0, H0)
