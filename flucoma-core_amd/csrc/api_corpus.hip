@@ -1681,7 +1681,7 @@ int fluhip_corpus_resynth_dev(fluhip_corpus* c, float* out_dev)
   if (rc) return rc;
   rc = get_twiddle(ctx, c->fft, &ttab);
   if (rc) return rc;
-  // Batched form (kernels_stft2.hip resynth_seq_kernel): every component of a group of buffers in one launch, the
+  // Batched form (kernels_resynth_batch.hip resynth_seq_kernel): every component of a group of buffers in one launch, the
   // overlap-add in registers -- no windowed frames in memory (the per-buffer path below writes and re-reads K T win doubles
   // per buffer: 58 GB each way on the bench shard, 85 ms against 113 ms for 200 iterations).  FLUHIP_RESYNTH_BATCH=0 off.
   static const int batchEnv = [] { const char* e = fluhip::ab_getenv("FLUHIP_RESYNTH_BATCH"); return e ? std::atoi(e) : 1; }();

@@ -69,7 +69,7 @@ static int check_feature_params(fluhip_ctx* ctx, bool mfcc, int64_t fft, int64_t
   return FLUHIP_OK;
 }
 
-// fused form (kernels_stft2.hip stft_feat_kernel): the magnitudes never leave the chip.
+// fused form (kernels_stft_feat.hip stft_feat_kernel): the magnitudes never leave the chip.
 // Every bin must lie on the rising edge of at most one band and the falling edge of the band below it, with the
 // bins of each edge contiguous: then band b = (sum of up[f] m[f] over interval b) + (sum of dn[f] m[f] over interval
 // b + 1), interval s = the bins between centres s and s + 1.  True of any filter bank whose triangles are wider than
@@ -271,7 +271,7 @@ static int features_common(fluhip_ctx* ctx, bool mfcc, const float* audio, int64
   HIPCHK(ctx, dDct.alloc(dct.size() * sizeof(double), false, s));
   HIPCHK(ctx, hipMemcpyAsync(dFilt.p, filtT.data(), filtT.size() * sizeof(double), hipMemcpyHostToDevice, s));
   HIPCHK(ctx, hipMemcpyAsync(dDct.p, dct.data(), dct.size() * sizeof(double), hipMemcpyHostToDevice, s));
-  // ---- fused form (kernels_stft2.hip stft_feat_kernel): the magnitudes never leave the chip --------------------------
+  // ---- fused form (kernels_stft_feat.hip stft_feat_kernel): the magnitudes never leave the chip --------------------------
   {
     std::vector<double> up, dn;
     std::vector<short> slot;

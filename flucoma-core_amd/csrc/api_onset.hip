@@ -82,7 +82,7 @@ int onset_raw_dev(const OnsetRun& r, int64_t nb, double* raw)
   if (rc) return rc;
   if (plan.form == kOnsetFormOnChip)
   {
-    // one launch over all buffers, no workspace: the spectra stay in the LDS (kernels_stft2.hip, onset_fused_kernel)
+    // one launch over all buffers, no workspace: the spectra stay in the LDS (kernels_onset_fused.hip, onset_fused_kernel)
     StftArgs sa = st.args(r.a32, r.a64, r.n, r.stride, nb, T, r.base);
     OnsetFusedArgs o;
     o.function = r.function; o.history = plan.history;

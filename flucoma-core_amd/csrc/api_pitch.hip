@@ -3,7 +3,7 @@
 //   fluhip_debug_pitch_curve_f64  the curve each of them searches (normalised yin, harmonic product, cepstrum)
 //   fluhip_bufpitch_f32           NRTPitchClient  clients/rt/PitchClient.hpp, common/FluidNRTClientWrapper.hpp:551-660
 //   fluhip_debug_pitch_plan
-// fft 1024 / 2048 / 4096 with an even window run the on-chip form (pitch_fused_kernel, kernels_stft2.hip): one launch from
+// fft 1024 / 2048 / 4096 with an even window run the on-chip form (pitch_fused_kernel, kernels_pitch_fused.hip): one launch from
 // the samples to (f0, confidence), or to the log-magnitudes of the cepstrum.  Everything else, and the two entry points
 // that are given magnitudes, run the two-pass form: the kernels are in kernels_pitch.hip (fluhip_pitch.h); the magnitudes
 // come from launch_stft, YinFFT's second transform is the same launch over the symmetric squared magnitudes (window = hop

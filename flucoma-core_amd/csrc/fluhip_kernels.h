@@ -63,7 +63,7 @@ struct StftArgs
 };
 
 void launch_stft(const StftArgs& a, hipStream_t s);
-// block form (kernels_stft2.hip): the same transform writing the frame-major magnitudes (a.mag) AND the bin-major
+// block form (kernels_stft_block.hip): the same transform writing the frame-major magnitudes (a.mag) AND the bin-major
 // copy magT [B][*][ldMagT] in one pass; false when the shape has no block form (launch_stft + launch_transpose then)
 bool launch_stft_block(const StftArgs& a, double* magT, int64_t magTStride, int64_t ldMagT, hipStream_t s);
 // power-of-two fft up to 65536; sizes whose frame does not fit the LDS (above 8192) run their passes through a
@@ -379,7 +379,7 @@ struct FeatLayout
 };
 FeatLayout features_layout(int64_t F, int64_t bandsPad);
 bool launch_features(const FeatArgs& a, hipStream_t s); // false, and nothing launched, when !features_layout(F, bandsPad).fits
-// fused form (kernels_stft2.hip): STFT -> mel bands [-> DCT] without the magnitudes leaving the chip.  up / dn / slot
+// fused form (kernels_stft_feat.hip): STFT -> mel bands [-> DCT] without the magnitudes leaving the chip.  up / dn / slot
 // [64 * stft_features_bins_per_lane(fft)]: rising- and falling-edge weight of every bin and the interval boundary a
 // bin closes (or -1); false when the shape has no fused form
 struct StftArgs;
@@ -415,7 +415,7 @@ void launch_resynth(const ResynthArgs& a, hipStream_t s);
 // dst[c][r] = src[r][c], floats (rows x cols, row strides lds / ldd)
 void launch_transpose_f32(const float* src, int64_t lds, float* dst, int64_t ldd, int rows, int64_t cols, hipStream_t s);
 
-// Batched resynthesis (kernels_stft2.hip, resynth_seq_kernel): every component of every buffer of a corpus in one launch.
+// Batched resynthesis (kernels_resynth_batch.hip, resynth_seq_kernel): every component of every buffer of a corpus in one launch.
 // A wavefront owns (buffer, component, a run of hop slots) and walks the frames that cover the run IN ORDER: masked
 // spectrum -> inverse real transform in registers (the forward passes of the STFT kernels on the conjugate) -> window ->
 // added to 2 win doubles of running overlap-add state held in registers; after each frame the oldest `hop` samples are

@@ -9,7 +9,7 @@ namespace fluhip {
 
 enum : int
 {
-  kOnsetFormOnChip = 0, // onset_fused_kernel (kernels_stft2.hip): transform and reduction in one launch, spectra in the LDS
+  kOnsetFormOnChip = 0, // onset_fused_kernel (kernels_onset_fused.hip): transform and reduction in one launch, spectra in the LDS
   kOnsetFormTwoPass = 1 // the STFT launch writes the complex spectra of a round to a workspace, onset_reduce_kernel reads them
 };
 constexpr int kOnsetFunctions = 10;
@@ -35,7 +35,7 @@ struct OnsetPlan
   int transforms = 1; // 2 with a frame delta
   int run = 0;        // on-chip form: frames a workgroup writes (kOnsetRun); 0 in the two-pass form
 };
-// the sizes the on-chip FFT core of kernels_stft2.hip is built for: fft 1024, 2048, 4096 with an even window
+// the sizes the on-chip FFT core (fft_core.h) is built for: fft 1024, 2048, 4096 with an even window
 bool onset_fused_supported(int64_t win, int64_t fft);
 OnsetPlan onset_plan(int64_t fft, int64_t win, int function, int64_t frameDelta);
 

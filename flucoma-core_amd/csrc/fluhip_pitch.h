@@ -16,7 +16,7 @@ enum : int
 };
 enum : int
 {
-  kPitchFormOnChip = 0, // pitch_fused_kernel (kernels_stft2.hip): transform and pitch in one launch, magnitudes in the LDS
+  kPitchFormOnChip = 0, // pitch_fused_kernel (kernels_pitch_fused.hip): transform and pitch in one launch, magnitudes in the LDS
   kPitchFormTwoPass = 1 // the STFT launch writes the magnitudes of a round to a workspace, the kernels here read them
 };
 constexpr int kPitchRun = 32; // consecutive frames of one buffer a workgroup of the on-chip form writes
@@ -29,7 +29,7 @@ struct PitchPlan
   int run = 0;        // on-chip form: frames a workgroup writes (kPitchRun); 0 in the two-pass form
   int transforms = 1; // 2 for YinFFT (the transform of the squared magnitudes)
 };
-// the sizes the on-chip FFT core of kernels_stft2.hip is built for: fft 1024, 2048, 4096 with an even window
+// the sizes the on-chip FFT core (fft_core.h) is built for: fft 1024, 2048, 4096 with an even window
 bool pitch_fused_supported(int64_t win, int64_t fft);
 PitchPlan pitch_plan(int64_t fft, int64_t win, int algorithm);
 

@@ -7,7 +7,7 @@
 //   onset_reduce_kernel  one wavefront per frame: every bin of the frame's spectrum against the one or two spectra before it
 //                        (zero spectra before the start) or against the second transform of a frame-delta form; one double
 //                        per frame.  The spectra are those the STFT launch of the round wrote (the two-pass form; the
-//                        on-chip form for fft 1024 / 2048 / 4096 is onset_fused_kernel, kernels_stft2.hip).
+//                        on-chip form for fft 1024 / 2048 / 4096 is onset_fused_kernel, kernels_onset_fused.hip).
 //   onset_filter_kernel  one thread per frame: the value minus the median of the last filterSize values.
 //   onset_detect_kernel  one wavefront per buffer: threshold crossings in parallel, the debounce as a scan over them.
 // The order of a frame's sum is fixed: lane l adds the bins l, l + 64, l + 128, ... in that order, the 64 partial sums

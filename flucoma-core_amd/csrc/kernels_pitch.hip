@@ -4,7 +4,7 @@
 //   algorithm::CepstrumF0     include/flucoma/algorithms/public/CepstrumF0.hpp:44-75, DCT.hpp:36-62
 //   algorithm::PeakDetection  include/flucoma/algorithms/util/PeakDetection.hpp:30-71
 // The kernels here read the magnitudes a round's STFT launch left in a workspace (the two-pass form), doubles throughout;
-// the per-frame arithmetic is in pitch_terms.h, which the on-chip form (pitch_fused_kernel, kernels_stft2.hip) shares:
+// the per-frame arithmetic is in pitch_terms.h, which the on-chip form (pitch_fused_kernel, kernels_pitch_fused.hip) shares:
 //   pitch_sym_kernel       the even-symmetric squared magnitudes of a frame as `fft` real samples; the STFT launch
 //                          transforms them a second time (rectangular window, hop = window = fft)
 //   pitch_yin_norm_kernel  one wavefront per frame: 2 sum(sq) - Re, then the running-sum normalisation as a wavefront scan

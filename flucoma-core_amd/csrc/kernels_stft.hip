@@ -313,7 +313,7 @@ __device__ __forceinline__ void stockham_pass(d2 (&pts)[NB * R], d2* buf, const 
 }
 
 #ifdef FLUHIP_AB_SWITCHES // round 1's wave-per-frame kernel: production reaches it for no shape any more (the block form of
-                         // kernels_stft2.hip covers fft 1024 / 2048 / 4096 with an even window); kept for the A/B build (FLUHIP_STFT_BLOCK=0)
+                         // kernels_stft_block.hip covers fft 1024 / 2048 / 4096 with an even window); kept for the A/B build (FLUHIP_STFT_BLOCK=0)
 template <int R1, int R2, int R3, int MAXW>
 __global__ __launch_bounds__(64 * MAXW) void stft_wave_kernel(StftKArgs a)
 {
@@ -694,7 +694,7 @@ void launch_stft(const StftArgs& a, hipStream_t s)
     // wave-per-frame kernels: power-of-two fft with an even window (pairs of window values)
     if (!generic && (a.win % 2) == 0)
     {
-      // the block form (kernels_stft2.hip) without its bin-major output is the faster wave-per-frame kernel
+      // the block form (kernels_stft_block.hip) without its bin-major output is the faster wave-per-frame kernel
       if (launch_stft_block(a, nullptr, 0, 0, s)) return;
 #ifdef FLUHIP_AB_SWITCHES // (only with FLUHIP_STFT_BLOCK=0: the block form takes these sizes)
       if (a.fft == 2048) { launch_stft_wave<16, 8, 8, 8>(k, s); return; }

@@ -1,5 +1,5 @@
 // onset_terms.h -- device arithmetic of the onset detection functions, shared by the two forms of the curve kernel:
-// onset_reduce_kernel (kernels_onset.hip, spectra from a workspace) and onset_fused_kernel (kernels_stft2.hip, spectra in
+// onset_reduce_kernel (kernels_onset.hip, spectra from a workspace) and onset_fused_kernel (kernels_onset_fused.hip, spectra in
 // the LDS).  One definition, so that both forms add the same terms in the same order:
 // lane l visits the bins l, l + 64, l + 128, ... in that order and adds each bin's term to its partial sum; the 64 partial
 // sums then meet in a butterfly (xor 32, 16, ... 1).  Every function switches floating-point contraction off for itself:

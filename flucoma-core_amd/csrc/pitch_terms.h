@@ -1,5 +1,5 @@
 // pitch_terms.h -- the per-frame arithmetic of BufPitch, one wavefront per frame, shared by the two kernel forms: the
-// kernels of kernels_pitch.hip read a frame's row from a workspace in memory, pitch_fused_kernel (kernels_stft2.hip) reads
+// kernels of kernels_pitch.hip read a frame's row from a workspace in memory, pitch_fused_kernel (kernels_pitch_fused.hip) reads
 // it from the wavefront's staging buffer in the LDS.  One text, so both forms sum and compare in the same order: lane l
 // takes the bins l, l + 64, ... in that order, the 64 partial results meet in a butterfly (xor 32 .. 1); the scan walks
 // chunks of 64 with a carry.  Contraction is switched off in every function (the fused kernel's file is compiled with the
@@ -15,7 +15,7 @@ namespace pitchdev {
 constexpr double kInf = __builtin_huge_val();
 constexpr double kMinNormal = 2.2250738585072014e-308; // DBL_MIN
 
-// YinFFT's squared magnitude.  The block STFT starts a bin's sum of squares from DBL_MIN (kernels_stft2.hip, mag_sumsq), so an
+// YinFFT's squared magnitude.  The block STFT starts a bin's sum of squares from DBL_MIN (fft_core.h, mag_sumsq), so an
 // exactly zero bin arrives as sqrt(DBL_MIN); its square is the zero it stands for.  YinFFT is invariant under scaling, so
 // without this digital silence would be analysed as a flat spectrum where the reference returns (0, 0).
 __device__ __forceinline__ double yin_square(double v)

@@ -8,7 +8,7 @@
 //                                          latency / hop frames dropped, output resized to frames x (channels * features)
 //                                          at sampleRate / hop, feature i of channel j in buffer channel i + j * features
 // The reference pushes hop samples at a time through the real-time client; here the channels of the job are one batch of
-// equal-length buffers for the fused STFT -> mel -> [DCT] kernel (kernels_stft2.hip: stft_feat_kernel), whose frame
+// equal-length buffers for the fused STFT -> mel -> [DCT] kernel (kernels_stft_feat.hip: stft_feat_kernel), whose frame
 // positions are the closed form of that bookkeeping (tests/test_oracle.py derives it from the FluidSource model).
 #pragma once
 

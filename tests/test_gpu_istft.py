@@ -175,7 +175,7 @@ def run_corpus(ctx, win, fft, hop, B, n, K, seed):
         check_corpus_buffer(ctx, f"{win}_{fft}_{hop} B{B} n{n} K{K} buffer {b}", audio[b], out[b], W1[b], H1[b], win, fft, hop)
 
 
-# Which form a corpus' resynthesis takes is resynth_batch_supported's rule (kernels_stft2.hip), which no entry point reports:
+# Which form a corpus' resynthesis takes is resynth_batch_supported's rule (kernels_resynth_batch.hip), which no entry point reports:
 # an even window that is a multiple of the hop, fft 2048 with a hop of 256 / 512 / 1024 or fft 1024 with 128 / 256 / 512 --
 # every shape below but PER_BUFFER's fft 512.  Rank 3 packs two (buffer, run) pairs into a workgroup, rank 8 takes the rows
 # shared through the LDS, rank 9 leaves seven idle wavefronts at the barriers; the odd n puts every other component's

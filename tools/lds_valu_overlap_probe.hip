@@ -1,6 +1,6 @@
 // lds_valu_overlap_probe.hip -- do FP64 VALU work and LDS traffic of DIFFERENT wavefronts of a SIMD overlap on gfx950?
 //
-// The fused feature kernel (kernels_stft2.hip stft_feat_kernel) runs 16 wavefronts per CU whose frames alternate butterfly
+// The fused feature kernel (kernels_stft_feat.hip stft_feat_kernel) runs 16 wavefronts per CU whose frames alternate butterfly
 // passes (FP64 VALU) with LDS exchanges; switched on one at a time the parts ADD UP to the kernel's time (round 3), PMC shows
 // VALU ~46 % busy + LDS array ~42 % active, and none of round 4's rearrangements (fewer / more wavefronts, two frames per
 // wavefront, priorities, LDS bytes moved to the L1) changed it.  This probe takes the kernel apart into its two ingredients:
