@@ -1,4 +1,4 @@
-// api_internal.h -- what the translation units of the C-ABI layer share (api_core / api_corpus / api_algorithms /
+// api_internal.h -- what the translation units of the C-ABI layer share (api_core / api_corpus / corpus_plan / corpus_loop / api_algorithms /
 // api_features / api_frames / api_cross / api_novelty / api_onset / api_hpss / api_pitch .hip): the context and corpus
 // structures, the caching device buffer, the scaffold of a call (guarded, DEV_ALLOC, check_fft_settings, StftSetup) and the
 // helpers one unit defines for the others.  The clients' frame counts are in client_frames.h (host only, shared with
@@ -290,22 +290,29 @@ int check_fft_settings(fluhip_ctx* ctx, int64_t win, int64_t fft, int64_t hop);
 // ---------------------------------------------------------------------------------------
 // corpus
 // ---------------------------------------------------------------------------------------
-// the schedule of the factor updates of a shape as data: api_corpus.hip decide_update_plan (round 6)
+// the schedule of the factor updates of a shape as data: corpus_plan.hip decide_update_plan (round 6)
 struct UpdatePlan
 {
   int variant = 5;      // 5: kernels_nmf5.hip (ranks up to 128), 0: the any-rank path
   int64_t Kp = 0;       // rank the arrays are laid out for
-  int Kc = 0;           // rank the factor updates compute (off-size ranks)
+  int Kc = 0;           // rank the factor updates compute (off-size ranks: 24 on arrays of rank 32; 40 / 48 / 56 on 64; 72 .. 112 in eights on 128), else Kp
   int nsplitW = 1, nsplitH = 1;
-  bool lazy = false, sideW = false, strip = false, stripBin = false, stripTile = false, useLists = false;
+  bool lazy = false;    // deferred normalisation of W inside the iteration loop (fluhip_kernels.h UpdateArgs::nrm): the two-launch-per-factor fast path
+  bool sideW = false;   // ... with the Nyquist bin of the W update as a side column
+  bool strip = false;   // frame-strip schedule of a single large buffer at rank <= 16 (kernels_nmf_strip.hip)
+  // ... with the W update as its own launch over bin strips (nmf_binstrip_kernel; round 4), or as the bin-tiled launch
+  // (kernels_nmf_bintile.hip; round 5): A/B build only
+  bool stripBin = false, stripTile = false;
+  bool useLists = false; // the factor updates run from work lists (ragged corpora; small equal-length ones)
   int stripsW = 0;      // statistics records per buffer of a W update (its wavefronts, or the finalize's chunks when split)
   int stripsH = 0;      // wavefronts per buffer of a uniform H update (0: lists / frame strips / any-rank)
+  // H update in two launches (plan_tail): the first tailStripsH strips of every buffer (tailColsH frames) as whole
+  // contractions, the rest (tailRestH strips) with the contraction cut into tailSplitH pieces; 0 = one launch
   int tailSplitH = 0, tailStripsH = 0, tailRestH = 0, tailColsH = 0;
   // workspaces in doubles: what the launches of this plan index (plan_updates allocates exactly these)
   int64_t partDoubles = 0, dpartDoubles = 0, csumDoubles = 0, wscratchDoubles = 0, colPartDoubles = 0, stripPartDoubles = 0,
           wideDoubles = 0;
 };
-void decide_update_plan(int64_t B, int64_t T, int64_t F, int64_t K, UpdatePlan& p);
 
 struct fluhip_corpus
 {
@@ -317,44 +324,45 @@ struct fluhip_corpus
   bool stftOnly = false; // spectrogram-only use (fluhip_stft_*): one layout of the magnitudes, no factor workspaces
   const float* audioDev = nullptr; // borrowed or owned (audioOwn)
   DevBuf audioOwn, mag, magT, Wf, H1, spec, part, dpart, stage, hmax, normScratch;
-  int nsplitW = 1, nsplitH = 1;
-  // H update in two launches (plan_tail): the first tailStripsH strips of every buffer (tailColsH frames) as whole
-  // contractions, the rest (tailRestH strips) with the contraction cut into tailSplitH pieces; 0 = one launch
-  int tailSplitH = 0, tailStripsH = 0, tailRestH = 0, tailColsH = 0;
-  // deferred normalisation of W inside the iteration loop (fluhip_kernels.h UpdateArgs::nrm)
-  bool lazy = false;     // the shape takes the two-launch-per-factor fast path
-  bool sideW = false;    // ... with the Nyquist bin of the W update as a side column
-  bool wPending = false; // W in memory is W' = W diag(wnorm)
-  bool sideFromH = false; // the H update enqueued last left the next W update's side-column partials (sideFromHSlices per buffer)
-  bool colsumWInPlace = false; // the W update enqueued last left the column sums of the new W' in the H update's denominator slots (launch_wnorm_combine)
-  int sideFromHSlices = 0;
-  int sideGen = 0;        // which of the two side-partial areas of wscratch holds them (an H update reads one and fills the other)
-  bool normDue = false;   // the W update enqueued last left its norm combine to the H update behind it
-  bool planError = false; // a launch did not take the form its dry run announced (reported by corpus_iterate)
-  int stripsW = 0;       // wavefronts per buffer of the W update (statistics partials)
+  UpdatePlan plan; // of this corpus's shape: written once, by plan_updates, and only read by the loop
+  // what changes from launch to launch of the iteration loop (corpus_loop.hip)
+  struct RunState
+  {
+    bool wPending = false; // W in memory is W' = W diag(wnorm)
+    bool sideFromH = false; // the H update enqueued last left the next W update's side-column partials (sideFromHSlices per buffer)
+    bool colsumWInPlace = false; // the W update enqueued last left the column sums of the new W' in the H update's denominator slots (launch_wnorm_combine)
+    int sideFromHSlices = 0;
+    int sideGen = 0;        // which of the two side-partial areas of wscratch holds them (an H update reads one and fills the other)
+    bool normDue = false;   // the W update enqueued last left its norm combine to the H update behind it
+    bool planError = false; // a launch did not take the form its dry run announced (reported by corpus_iterate)
+    bool colPartValid = false; // the last W update filled colPart (the H update behind then takes its column sums from there)
+    bool stripReady = false;     // the numerator partials of the next W update are in stripPart
+    bool stripNormFresh = false; // wnorm holds the column norms of the W' in memory
+    bool stripStatsValid = false; // the column-statistics records of generation stripGen describe the W in memory
+    int stripGen = 0;
+    bool stripSideReady = false; // the Nyquist bin's numerator partials of the next W update are in tileWork
+    // window of buffers the next enqueue_iteration works on (0 buffers = all): corpora of several rounds of wavefronts
+    // run their iterations round by round (corpus_iterate_loop)
+    int64_t winB0 = 0, winB = 0;
+    int winStripsW = 0, winStripsH = 0;
+    // a call of the loop starts with nothing handed from one launch to the next; what describes the arrays in memory (wPending,
+    // sideGen, stripGen, stripStatsValid, stripNormFresh) survives from call to call
+    void begin_call()
+    {
+      sideFromH = false; // (side-column partials an H update leaves are only ever used by the W update enqueued right behind it)
+      colPartValid = false;
+      colsumWInPlace = false;
+      normDue = false;
+    }
+  } run;
   DevBuf wnorm, wscratch, csumScratch, wideScratch;
   DevBuf colPart;            // [B][stripsW][Kp]: column sums of the rows of W' each wavefront of the last W update wrote (UpdateArgs::colOut)
-  bool colPartValid = false; // ... and whether that launch filled it (the H update behind then takes its column sums from there)
   DevBuf clk; // UpdateArgs::clk: 4 words for the W update's launches, 4 for the H update's
   // events on the context stream around the last iteration loop (behind the host-side initialisation, in front of
   // nothing but the loop's own launches): fluhip_corpus_last_loop_ms -- device time of the loop for tools/perf_matrix.py
   hipEvent_t loopEv0 = nullptr, loopEv1 = nullptr;
   bool loopTimed = false;
-  // frame-strip schedule of a single large buffer at rank <= 16 (kernels_nmf_strip.hip)
-  bool strip = false;
-  bool stripReady = false;     // the numerator partials of the next W update are in stripPart
-  bool stripNormFresh = false; // wnorm holds the column norms of the W' in memory
-  bool stripStatsValid = false; // the column-statistics records of generation stripGen describe the W in memory
-  int stripGen = 0;
-  DevBuf stripPart;
-  // ... with the W update as its own launch over bin strips (kernels_nmf_strip.hip nmf_binstrip_kernel; round 4): no
-  // numerator partials of the whole matrix, no reduce launch, the strip kernel runs its H phase only
-  bool stripBin = false;
-  DevBuf binWork;
-  int Kc = 0;                  // compute rank of the factor updates (off-size ranks: 24 on arrays of rank 32; 40 / 48 / 56 on 64; 72 .. 112 in eights on 128), else Kp
-  bool stripTile = false;      // round 5: the W update as the bin-tiled launch (kernels_nmf_bintile.hip)
-  bool stripSideReady = false; // the Nyquist bin's numerator partials of the next W update are in tileWork
-  DevBuf tileWork;
+  DevBuf stripPart, binWork, tileWork; // frame-strip schedule: numerator partials; work areas of the bin-strip / bin-tiled W update
   bool haveMag = false, haveFactors = false;
   bool touched = false; // work that reads the audio has been enqueued on the compute stream
   // Seed / Fixed factors of the batched form (fluhip_corpus_set_factors): host copies, [B][K][F] and [B][K][T] floats
@@ -363,11 +371,6 @@ struct fluhip_corpus
   // the longest buffer (the strides of every array); frames past a buffer's own count are zero padding that stays zero.
   // The factor updates run kernels_nmf5.hip in work-list mode: one WaveDesc per wavefront, dealt by work.
   bool ragged = false;
-  bool useLists = false; // the factor updates run from work lists (ragged corpora; small equal-length ones)
-  // window of buffers the next enqueue_iteration works on (0 buffers = all): corpora of several rounds of wavefronts
-  // run their iterations round by round (corpus_iterate_loop)
-  int64_t winB0 = 0, winB = 0;
-  int winStripsW = 0, winStripsH = 0;
   std::vector<int64_t> nOf; // samples per buffer
   std::vector<int> tOf;     // frames per buffer
   DevBuf nTab, tTab;        // the same on the device
@@ -375,9 +378,12 @@ struct fluhip_corpus
   {
     DevBuf list, splitTab;
     int wgs = 0, ng = 0, partial = 0, maxSplit = 1;
-    int64_t nPartials = 0;
-    int statParts = 0; // column-statistics parts per buffer (W update)
   } listW, listH;
+  ~fluhip_corpus() // (also the stack corpora of the algorithm-level entry points hand their loop events back)
+  {
+    if (loopEv0) ctx->eventPool.push_back(loopEv0);
+    if (loopEv1) ctx->eventPool.push_back(loopEv1);
+  }
   int64_t device_bytes() const
   {
     return (int64_t) (audioOwn.bytes + mag.bytes + magT.bytes + Wf.bytes + H1.bytes + spec.bytes +
@@ -395,9 +401,10 @@ struct FactorInit
   bool sharedW = false, sharedH = false;
 };
 
-// api_corpus.hip
+// corpus_plan.hip
 int update_variant(int Kp);
 int64_t padded_rank(int64_t K);
+// api_corpus.hip
 int plan_updates(fluhip_ctx* ctx, fluhip_corpus* c);
 int corpus_alloc(fluhip_ctx* ctx, fluhip_corpus* c);
 int check_rank(fluhip_ctx* ctx, int64_t T, int64_t F, int64_t K);
@@ -405,6 +412,7 @@ int check_shape(fluhip_ctx* ctx, int64_t n, int64_t win, int64_t fft, int64_t ho
 int corpus_stft(fluhip_corpus* c, const float* a32, const double* a64, int64_t audioStride, bool magOnly = false);
 void draw_uniform(int64_t seed, size_t count, std::vector<double>& out);
 int corpus_init_factors(fluhip_corpus* c, int64_t seed, const int64_t* seeds, const FactorInit& fi);
+// corpus_loop.hip
 int corpus_iterate(fluhip_corpus* c, int64_t iters, bool updateW, bool updateH, fluhip_progress_fn progress, void* user);
 
 // api_features.hip

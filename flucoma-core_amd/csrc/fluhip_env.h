@@ -21,6 +21,13 @@ inline const char* ab_getenv(const char* name)
 #endif
 }
 
+// an integer switch (`dflt` when unset, and always in the production library); call sites keep it in a `static const`
+inline int ab_int(const char* name, int dflt)
+{
+  const char* e = ab_getenv(name);
+  return e ? std::atoi(e) : dflt;
+}
+
 constexpr bool kAbSwitches =
 #ifdef FLUHIP_AB_SWITCHES
     true;

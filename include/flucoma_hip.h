@@ -621,20 +621,20 @@ int fluhip_corpus_plan(const fluhip_corpus* c, int64_t* out8);
 int64_t fluhip_debug_plan_lists(int64_t count, const int64_t* frames, int64_t bins, int64_t K, int which, int32_t* desc,
                                 int64_t cap, int32_t* info8);
 
-/* Likewise for the two-launch form of the H update (api_corpus.hip plan_tail): `count` equal-length buffers of `frames` frames and
+/* Likewise for the two-launch form of the H update (corpus_plan.hip plan_tail): `count` equal-length buffers of `frames` frames and
  * `bins` bins at rank K.  out4 = {pieces of the tail launch's contraction (0: the update stays one launch), strips per buffer
  * of the first launch, strips per buffer of the tail launch, frames per buffer in the first launch}. */
 int fluhip_debug_plan_tail(int64_t count, int64_t frames, int64_t bins, int64_t K, int64_t* out4);
 /* Which schedule family an equal-length corpus of that shape gets when nothing else decides first (a single buffer of rank <= 16
  * that fits the frame-strip schedule never asks): 1 = the work lists, 0 = the uniform schedule; -1: bad arguments.  The rules are
- * measured ones (api_corpus.hip list_plan_pays, profiles/r03/plan_regimes.txt); the CPU tests pin them for the BASELINE shapes. */
+ * measured ones (corpus_plan.hip list_plan_pays, profiles/r03/plan_regimes.txt); the CPU tests pin them for the BASELINE shapes. */
 int fluhip_debug_plan_kind(int64_t count, int64_t frames, int64_t bins, int64_t K);
 /* What the H update of an equal-length corpus of that shape takes over from the launches that used to run between the two
  * factor updates (kernels_nmf5.hip SIDEQ forms; no device needed): bit 0 = the next W update's side column (its last bin)
  * comes out of this launch's epilogue, bit 1 = the norm combine of the W update in front is done in its prologue; 0 = neither
  * (rank above 64, work lists, two-launch H update, no side column at this bin count); -1: bad arguments. */
 int fluhip_debug_plan_h_update(int64_t count, int64_t frames, int64_t bins, int64_t K);
-/* The WHOLE schedule of an equal-length corpus of that shape as data, without a device (api_corpus.hip decide_update_plan: the
+/* The WHOLE schedule of an equal-length corpus of that shape as data, without a device (corpus_plan.hip decide_update_plan: the
  * one function fluhip_corpus_create plans from).  out32 =
  *   0 kernel family (5 / 0)   1 pieces of the W update's contraction   2 of the H update's   3 deferred normalisation
  *   4 Nyquist bin as a side column   5 statistics records per buffer of a W update   6 padded rank   7 computed rank

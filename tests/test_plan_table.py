@@ -1,5 +1,5 @@
 """The schedule of the factor updates as DATA: `fluhip_debug_plan_shape` is the planner's whole answer for a
-shape -- api_corpus.hip decide_update_plan, the one function fluhip_corpus_create plans from -- without a device.  Here:
+shape -- corpus_plan.hip decide_update_plan, the one function fluhip_corpus_create plans from -- without a device.  Here:
 
   * the pinned plans of the BASELINE shapes and of every row of tools/perf_matrix.py (tests/golden/plans_r06.json, minted by
     tools/make_plan_fixture.py; the fields the GPU runs of profiles/r06/perf_matrix_v0.json recorded agree with it);
