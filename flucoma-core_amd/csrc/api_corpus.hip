@@ -685,6 +685,35 @@ int fluhip_corpus_read_f64(fluhip_corpus* c, double* mag, double* W1, double* H1
   return FLUHIP_OK;
 }
 
+// Diagnostic: the corpus's layouts as they lie on the device, padding included -- the frame-major magnitudes
+// [count][Tp][Fp] (readable after fluhip_corpus_stft_mag_only too, where fluhip_corpus_read_f64 refuses), the bin-major copy
+// the H update streams, [count][Fp][Tp], and (with keep_spectrum on) the complex spectrum [count][T][F][2].
+// dims5 = {count, Fp, Tp, T, F}; any array may be null (dims5 alone sizes the caller's arrays).
+int fluhip_debug_corpus_read_layouts_f64(fluhip_corpus* c, int64_t* dims5, double* mag, double* magT, double* spec)
+{
+  if (!c) return FLUHIP_ERROR;
+  fluhip_ctx* ctx = c->ctx;
+  if (dims5) { dims5[0] = c->B; dims5[1] = c->Fp; dims5[2] = c->Tp; dims5[3] = c->T; dims5[4] = c->F; }
+  if (!mag && !magT && !spec) return FLUHIP_OK;
+  if (!c->touched) return fail(ctx, "corpus has no spectrogram: no transform has run on it");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  if (mag) HIPCHK(ctx, hipMemcpyAsync(mag, c->mag.p, (size_t) c->B * c->Tp * c->Fp * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (magT)
+  {
+    if (!c->haveMag || !c->magT.p) return fail(ctx, "corpus has no bin-major magnitudes: call fluhip_corpus_stft first");
+    HIPCHK(ctx, hipMemcpyAsync(magT, c->magT.p, (size_t) c->B * c->Fp * c->Tp * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  if (spec)
+  {
+    if (!c->keepSpec || !c->spec.p)
+      return fail(ctx, "corpus has no spectrum: fluhip_corpus_keep_spectrum(c, 1) before the transform");
+    HIPCHK(ctx, hipMemcpyAsync(spec, c->spec.p, (size_t) c->B * c->T * c->F * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  return FLUHIP_OK;
+}
+
 int fluhip_corpus_plan(const fluhip_corpus* c, int64_t* out8)
 {
   if (!c || !out8) return FLUHIP_ERROR;

@@ -74,7 +74,7 @@ EXPORTS = [
     "fluhip_debug_onset_plan",
     "fluhip_hpss_planes_f64", "fluhip_bufhpss_f32", "fluhip_debug_hpss_plan",
     "fluhip_pitch_frames_f64", "fluhip_debug_pitch_curve_f64", "fluhip_bufpitch_f32", "fluhip_debug_pitch_plan",
-    "fluhip_debug_features_plan", "fluhip_debug_resynth_f64",
+    "fluhip_debug_features_plan", "fluhip_debug_resynth_f64", "fluhip_debug_corpus_read_layouts_f64",
 ]
 
 
@@ -188,6 +188,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.fluhip_corpus_writeback_dev.argtypes = [_vp, _vp, _vp]
     L.fluhip_corpus_writeback_host.argtypes = [_vp, _fp, _fp]
     L.fluhip_corpus_read_f64.argtypes = [_vp, _dp, _dp, _dp]
+    L.fluhip_debug_corpus_read_layouts_f64.argtypes = [_vp, _ip, _dp, _dp, _dp]
     L.fluhip_corpus_plan.argtypes = [_vp, _ip]
     L.fluhip_corpus_keep_spectrum.argtypes = [_vp, ctypes.c_int]
     L.fluhip_corpus_resynth_dev.argtypes = [_vp, _vp]
@@ -960,6 +961,19 @@ class Corpus:
         H1 = np.empty((self.count, self.T, self.K)) if factors else None
         self.ctx._check(self.ctx.lib.fluhip_corpus_read_f64(self.h, _d(m), _d(W1), _d(H1)))
         return m, W1, H1
+
+    def read_layouts_f64(self, mag=True, magT=True, spec=False):
+        """fluhip_debug_corpus_read_layouts_f64: (mag [count, Tp, Fp], magT [count, Fp, Tp], spec complex [count, T, F]) as
+        they lie on the device, padding included; None for what was not asked for"""
+        dims = (ctypes.c_int64 * 5)()
+        self.ctx._check(self.ctx.lib.fluhip_debug_corpus_read_layouts_f64(self.h, dims, None, None, None))
+        count, Fp, Tp, T, F = (int(v) for v in dims)
+        assert (count, T, F) == (self.count, self.T, self.F)
+        m = np.empty((count, Tp, Fp)) if mag else None
+        mT = np.empty((count, Fp, Tp)) if magT else None
+        sp = np.empty((count, T, F, 2)) if spec else None
+        self.ctx._check(self.ctx.lib.fluhip_debug_corpus_read_layouts_f64(self.h, None, _d(m), _d(mT), _d(sp)))
+        return m, mT, (sp[..., 0] + 1j * sp[..., 1] if spec else None)
 
 
 class RaggedCorpus(Corpus):

@@ -37,7 +37,8 @@ extern "C" {
  * fluhip_bufnoveltyslice_f32, fluhip_bufnoveltyfeature_f32, fluhip_debug_novelty_plan, fluhip_onset_curve_f64,
  * fluhip_onset_slices_f64, fluhip_bufonsetslice_f32, fluhip_bufonsetfeature_f32, fluhip_debug_onset_plan,
  * fluhip_debug_features_plan, fluhip_hpss_planes_f64, fluhip_bufhpss_f32, fluhip_debug_hpss_plan, fluhip_pitch_frames_f64,
- * fluhip_debug_pitch_curve_f64, fluhip_bufpitch_f32, fluhip_debug_pitch_plan, fluhip_debug_resynth_f64. */
+ * fluhip_debug_pitch_curve_f64, fluhip_bufpitch_f32, fluhip_debug_pitch_plan, fluhip_debug_resynth_f64,
+ * fluhip_debug_corpus_read_layouts_f64. */
 #define FLUHIP_ABI_VERSION 5
 
 /* clients/common/Result.hpp:24  enum class Status { kOk, kWarning, kError, kCancelled } */
@@ -600,6 +601,13 @@ int fluhip_corpus_resynth_host(fluhip_corpus* c, float* out);
 int fluhip_corpus_resynth_interleaved_host(fluhip_corpus* c, float* out, int64_t frame_stride);
 /* raw f64 results for parity tests: mag count x T x F, W1 count x K x F, H1 count x T x K */
 int fluhip_corpus_read_f64(fluhip_corpus* c, double* mag, double* W1, double* H1);
+/* Diagnostic for parity tests: the corpus's spectrogram layouts AS THEY LIE on the device, padding included.  dims5 (may be
+ * NULL) = { count, Fp, Tp, T, F } (Fp, Tp: bins and frames rounded up to 32, the leading dimensions); with every array NULL
+ * the call only reports them.  mag: count x Tp x Fp frame-major magnitudes (also after fluhip_corpus_stft_mag_only, where
+ * fluhip_corpus_read_f64 has no spectrogram to report); magT: count x Fp x Tp, the bin-major copy the H update streams
+ * (fluhip_corpus_stft only; columns T .. Tp and the frames past a ragged buffer's own are zero); spec: count x T x F x 2,
+ * the complex spectrum kept under fluhip_corpus_keep_spectrum (rows past a ragged buffer's own frames are not written). */
+int fluhip_debug_corpus_read_layouts_f64(fluhip_corpus* c, int64_t* dims5, double* mag, double* magT, double* spec);
 /* How the factor updates of this corpus are scheduled on the device (introspection for tests, benchmarks and
  * bug reports; no effect on results beyond summation order): out8 = { kernel form (5 = 4x4x4 MFMA + LDS-DMA, ranks up to
  * 128; 0 = the un-fused any-rank path above that), contraction splits of the W update, of the H update (low 16 bits;
