@@ -74,6 +74,8 @@ EXPORTS = [
     "fluhip_debug_onset_plan",
     "fluhip_hpss_planes_f64", "fluhip_bufhpss_f32", "fluhip_debug_hpss_plan",
     "fluhip_pitch_frames_f64", "fluhip_debug_pitch_curve_f64", "fluhip_bufpitch_f32", "fluhip_debug_pitch_plan",
+    "fluhip_spectralshape_frames_f64", "fluhip_bufspectralshape_f32", "fluhip_debug_chroma_filters_f64",
+    "fluhip_chroma_frames_f64", "fluhip_bufchroma_f32", "fluhip_debug_spectral_plan",
     "fluhip_debug_features_plan", "fluhip_debug_resynth_f64", "fluhip_debug_corpus_read_layouts_f64",
 ]
 
@@ -166,6 +168,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.fluhip_bufpitch_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _dbl, _dbl,
                                       ctypes.c_int, ctypes.c_int, _dbl, _fp, _ip]
     L.fluhip_debug_pitch_plan.argtypes = [_vp, _i64, _i64, ctypes.c_int, _ip]
+    L.fluhip_spectralshape_frames_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _dbl, _dbl, _dbl, ctypes.c_int, ctypes.c_int,
+                                                  _dbl, _dp]
+    L.fluhip_bufspectralshape_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _dbl, _dbl,
+                                              _dbl, ctypes.c_int, ctypes.c_int, _dbl, _fp, _ip]
+    L.fluhip_debug_chroma_filters_f64.argtypes = [_vp, _i64, _i64, _dbl, _dbl, _dp]
+    L.fluhip_chroma_frames_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _dbl, ctypes.c_int, _dbl, _dbl, _dbl, _dp]
+    L.fluhip_bufchroma_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, _i64, _dbl, ctypes.c_int, _dbl,
+                                       _dbl, _dbl, _fp, _ip]
+    L.fluhip_debug_spectral_plan.argtypes = [_vp, _i64, _i64, ctypes.c_int, _ip]
     L.fluhip_debug_features_plan.argtypes = [_vp, ctypes.c_int, _i64, _i64, _i64, _i64, _i64, _dbl, _dbl, _dbl, _ip]
     L.fluhip_corpus_create.argtypes = [_vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
     L.fluhip_corpus_create_ragged.argtypes = [_vp, _i64, _ip, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
@@ -823,6 +834,68 @@ class Context:
         window; run 32); form 1: two passes through a magnitude workspace (run 0)"""
         out = (_i64 * 4)()
         self._check(self.lib.fluhip_debug_pitch_plan(self.h, fft, win, algorithm, out))
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    # ---- BufSpectralShape, BufChroma (algorithms/public/SpectralShape.hpp, ChromaFilterBank.hpp and their clients) --------
+    def spectralshape_frames(self, mag, min_freq=0.0, max_freq=-1.0, rolloff_percent=95.0, unit=0, power=0, sample_rate=44100.0):
+        """SpectralShape::processFrame over magnitude planes [count,T,F] (or [T,F]) -> [count,T,7] doubles (centroid, spread,
+        skewness, kurtosis, rolloff, flatness, crest)"""
+        mag = self._pitch_mag(mag)
+        count, T, F = mag.shape
+        out = np.empty((count, T, 7))
+        self._check(self.lib.fluhip_spectralshape_frames_f64(self.h, _d(mag), count, T, F, F, min_freq, max_freq, rolloff_percent,
+                                                             unit, power, sample_rate, _d(out)))
+        return out
+
+    def bufspectralshape(self, audio, select=127, min_freq=0.0, max_freq=-1.0, rolloff_percent=95.0, unit=0, power=0, win=1024,
+                         fft=-1, hop=-1, padding_mode=1, sample_rate=44100.0):
+        """NRTSpectralShapeClient on mono buffers [count,n] (or [n]) -> float32 [count,selected,frames]"""
+        w, h, f = _i64(), _i64(), _i64()
+        self._check(self.lib.fluhip_fft_params(win, hop, fft, ctypes.byref(w), ctypes.byref(h), ctypes.byref(f), None))
+        audio = np.ascontiguousarray(np.atleast_2d(audio), dtype=np.float32)
+        count, n = audio.shape
+        Tr = _i64(0)
+        args = (w.value, f.value, h.value, padding_mode, select, min_freq, max_freq, rolloff_percent, unit, power, sample_rate)
+        self._check(self.lib.fluhip_bufspectralshape_f32(self.h, _f(audio), count, n, *args, None, ctypes.byref(Tr)))
+        out = np.empty((count, bin(select & 127).count("1"), Tr.value), dtype=np.float32)
+        self._check(self.lib.fluhip_bufspectralshape_f32(self.h, _f(audio), count, n, *args, _f(out), ctypes.byref(Tr)))
+        return out
+
+    def chroma_filters(self, num_chroma, F, ref=440.0, sample_rate=44100.0):
+        """the table of ChromaFilterBank::init, [num_chroma,F] doubles"""
+        out = np.empty((num_chroma, F))
+        self._check(self.lib.fluhip_debug_chroma_filters_f64(self.h, num_chroma, F, ref, sample_rate, _d(out)))
+        return out
+
+    def chroma_frames(self, mag, num_chroma=12, ref=440.0, normalize=0, min_freq=0.0, max_freq=-1.0, sample_rate=44100.0):
+        """ChromaFilterBank::processFrame over magnitude planes [count,T,F] (or [T,F]) -> [count,T,num_chroma] doubles"""
+        mag = self._pitch_mag(mag)
+        count, T, F = mag.shape
+        out = np.empty((count, T, max(0, num_chroma)))
+        self._check(self.lib.fluhip_chroma_frames_f64(self.h, _d(mag), count, T, F, F, num_chroma, ref, normalize, min_freq,
+                                                      max_freq, sample_rate, _d(out)))
+        return out
+
+    def bufchroma(self, audio, num_chroma=12, ref=440.0, normalize=0, min_freq=0.0, max_freq=-1.0, win=1024, fft=-1, hop=-1,
+                  padding_mode=1, sample_rate=44100.0):
+        """NRTChromaClient on mono buffers [count,n] (or [n]) -> float32 [count,num_chroma,frames]"""
+        w, h, f = _i64(), _i64(), _i64()
+        self._check(self.lib.fluhip_fft_params(win, hop, fft, ctypes.byref(w), ctypes.byref(h), ctypes.byref(f), None))
+        audio = np.ascontiguousarray(np.atleast_2d(audio), dtype=np.float32)
+        count, n = audio.shape
+        Tr = _i64(0)
+        args = (w.value, f.value, h.value, padding_mode, num_chroma, ref, normalize, min_freq, max_freq, sample_rate)
+        self._check(self.lib.fluhip_bufchroma_f32(self.h, _f(audio), count, n, *args, None, ctypes.byref(Tr)))
+        out = np.empty((count, num_chroma, Tr.value), dtype=np.float32)
+        self._check(self.lib.fluhip_bufchroma_f32(self.h, _f(audio), count, n, *args, _f(out), ctypes.byref(Tr)))
+        return out
+
+    def spectral_plan(self, fft, win, kind):
+        """(form, frames a workgroup of the on-chip form writes, transforms per frame, 1 when a GEMM follows) of SpectralShape
+        (kind 0) or Chroma (kind 1); form 0: one launch, magnitudes in the LDS (fft 1024 / 2048 / 4096, even window; run 32);
+        form 1: two passes through a magnitude workspace (run 0)"""
+        out = (_i64 * 4)()
+        self._check(self.lib.fluhip_debug_spectral_plan(self.h, fft, win, kind, out))
         return int(out[0]), int(out[1]), int(out[2]), int(out[3])
 
     # ---- profiling ----------------------------------------------------------------------

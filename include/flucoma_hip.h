@@ -38,7 +38,8 @@ extern "C" {
  * fluhip_onset_slices_f64, fluhip_bufonsetslice_f32, fluhip_bufonsetfeature_f32, fluhip_debug_onset_plan,
  * fluhip_debug_features_plan, fluhip_hpss_planes_f64, fluhip_bufhpss_f32, fluhip_debug_hpss_plan, fluhip_pitch_frames_f64,
  * fluhip_debug_pitch_curve_f64, fluhip_bufpitch_f32, fluhip_debug_pitch_plan, fluhip_debug_resynth_f64,
- * fluhip_debug_corpus_read_layouts_f64. */
+ * fluhip_debug_corpus_read_layouts_f64, fluhip_spectralshape_frames_f64, fluhip_bufspectralshape_f32,
+ * fluhip_debug_chroma_filters_f64, fluhip_chroma_frames_f64, fluhip_bufchroma_f32, fluhip_debug_spectral_plan. */
 #define FLUHIP_ABI_VERSION 5
 
 /* clients/common/Result.hpp:24  enum class Status { kOk, kWarning, kError, kCancelled } */
@@ -466,6 +467,73 @@ int fluhip_bufpitch_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int6
  * the LDS -- fft 1024, 2048 and 4096 with an even window.  form 1: the STFT launch leaves a round's magnitudes in a
  * workspace, the pitch kernels read them (run 0). */
 int fluhip_debug_pitch_plan(fluhip_ctx* ctx, int64_t fft, int64_t win, int algorithm, int64_t* out4);
+
+/* ---- BufSpectralShape, BufChroma (clients/rt/SpectralShapeClient.hpp, clients/rt/ChromaClient.hpp) -------- */
+/* algorithm::SpectralShape::processFrame on every frame of `count` magnitude planes: mag count x T x ld doubles (ld >= F,
+ * F = fft / 2 + 1 of a power-of-two fft from 4 to 65536), out count x T x 7 doubles: centroid, spread, skewness, kurtosis,
+ * rolloff, flatness, crest.  The reference's behaviour is kept:
+ *   - mag = max(mag, epsilon) comes before anything else;
+ *   - binHz = sr / (2 (F - 1)), minBin = ceil(min_freq / binHz), maxBin = min(floor(max_freq / binHz), F - 1), max_freq -1
+ *     meaning sr / 2 and anything above it capped there; maxBin <= minBin gives seven zeros;
+ *   - unit 1 (MIDI) with minBin 0: minBin becomes 1 and bin 1 takes bin 0's magnitude too;
+ *   - the segment is the maxBin - minBin bins minBin .. maxBin - 1 (bin maxBin is never read), yet its frequency axis is
+ *     LinSpaced(size, minBin binHz, maxBin binHz): the step is (maxBin - minBin) binHz / (size - 1), not binHz, and a
+ *     segment of one bin sits at maxBin binHz; the MIDI axis is 69 + 12 log(f / 440) log2E;
+ *   - the moments are sums about the centroid; the spread is returned as its square root, skewness and kurtosis divide by
+ *     powers of the unrooted spread;
+ *   - the rolloff is the first bin at which the running sum reaches rolloff_percent of the total, interpolated linearly
+ *     inside that bin (the first bin: its own frequency); if the sum never gets there the result is maxBin - 1, a bin
+ *     index.  rolloff_percent 100 depends on the order of summation in the reference itself and is not pinned: either the
+ *     last frequency step or maxBin - 1;
+ *   - flatness is 20 log10(max(exp(mean(log amp)) / mean(amp), epsilon)), crest 20 log10(max(max(amp) / mean(amp),
+ *     epsilon)); power 1 squares the clamped magnitudes.
+ * Defined here where the reference leaves its arrays: a quotient freq / binHz at or beyond F counts as F, and the segment
+ * the MIDI axis leaves empty (minBin 0 -> 1, maxBin 1) gives seven zeros.  Errors (nothing is clamped, nothing is written):
+ * min_freq < 0, max_freq < -1, rolloff_percent outside [0, 100], unit or power outside {0, 1}, a sample_rate that is not
+ * positive and finite, an fft that is no power of two in [4, 65536].  mag and out are host pointers. */
+int fluhip_spectralshape_frames_f64(fluhip_ctx* ctx, const double* mag, int64_t count, int64_t T, int64_t F, int64_t ld,
+                                    double min_freq, double max_freq, double rolloff_percent, int unit, int power,
+                                    double sample_rate, double* out);
+/* NRTSpectralShapeClient (SpectralShapeClient behind StreamingControl, clients/common/FluidNRTClientWrapper.hpp:551-660) for
+ * `count` equal-length mono buffers: audio count x n floats; padding_mode as in fluhip_bufmfcc_padded_f32; the client's
+ * latency is win, and the frames inside it are dropped without being transformed.  select: bits 0 .. 6 = centroid, spread,
+ * skew, kurtosis, rolloff, flatness, crest, in [1, 127]; the selected descriptors are the output channels in that order:
+ * out count x selected x frames floats (host).  With out NULL only *frames_out is written (size query).  sample_rate is
+ * the source buffer's.  The block STFT hands an exactly zero bin over as sqrt(DBL_MIN); the clamp to epsilon comes first,
+ * so digital silence is the all-epsilon frame of the reference. */
+int fluhip_bufspectralshape_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win, int64_t fft,
+                                int64_t hop, int padding_mode, int select, double min_freq, double max_freq,
+                                double rolloff_percent, int unit, int power, double sample_rate, float* out, int64_t* frames_out);
+/* Diagnostic: the table of algorithm::ChromaFilterBank::init, out num_chroma x F doubles.  As the reference builds it:
+ * fftSize = 2 (F - 1); freqs = LinSpaced(fftSize, 0, sr), i.e. fftSize points with the step sr / (fftSize - 1) and not
+ * sr / fftSize; then num_chroma log(freqs / (ref / 16)) log2E, freqs[0] = freqs[1] - 1.5 num_chroma; widths are the
+ * successive differences floored at 1; halfChroma = num_chroma / 2 in integers; the remainder is C's fmod(d + 10 num_chroma
+ * + halfChroma, num_chroma) - halfChroma, which goes negative for a large ref at a large fft; the weights are
+ * exp(-0.5 (2 r / width)^2), only the first F columns are kept and each is divided by its L2 norm over the rows. */
+int fluhip_debug_chroma_filters_f64(fluhip_ctx* ctx, int64_t num_chroma, int64_t F, double ref, double sample_rate, double* out);
+/* algorithm::ChromaFilterBank::processFrame on every frame of `count` magnitude planes (mag as above, never modified:
+ * the reference zeroes its caller's frame in place), out count x T x num_chroma doubles.  The range branch runs only if
+ * min_freq != 0 or max_freq != -1; inside it minBin = 0 for min_freq 0, else ceil(min_freq / binHz), maxBin =
+ * min(floor(min(max_freq, sr / 2) / binHz), F - 1), the bins 0 .. minBin INCLUSIVE and maxBin .. F - 1 are zeroed (both runs
+ * clamped to the frame).  Then the squares, the product with the filter table, times 2 / (fftSize num_chroma); normalize 1
+ * divides by max(sum, epsilon), 2 by max(max, epsilon).  A squared magnitude at or below DBL_MIN counts as zero, here as
+ * in fluhip_bufchroma_f32, whose block transform returns sqrt(DBL_MIN) for an exactly zero bin: silence is exactly 0.
+ * Errors: num_chroma outside [2, 128], ref outside (0, 22000], normalize outside {0, 1, 2}, min_freq < 0, a max_freq that is
+ * neither -1 nor >= 0 (the reference indexes at -1 in between), sample_rate and fft as above. */
+int fluhip_chroma_frames_f64(fluhip_ctx* ctx, const double* mag, int64_t count, int64_t T, int64_t F, int64_t ld,
+                             int64_t num_chroma, double ref, int normalize, double min_freq, double max_freq, double sample_rate,
+                             double* out);
+/* NRTChromaClient (ChromaClient behind StreamingControl) for `count` equal-length mono buffers, framed as
+ * fluhip_bufspectralshape_f32: out count x num_chroma x frames floats (host); out NULL is the size query. */
+int fluhip_bufchroma_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win, int64_t fft, int64_t hop,
+                         int padding_mode, int64_t num_chroma, double ref, int normalize, double min_freq, double max_freq,
+                         double sample_rate, float* out, int64_t* frames_out);
+/* Diagnostic: how (fft, win, kind) is computed, kind 0 SpectralShape, 1 Chroma: out4 = {form, frames a workgroup of the
+ * on-chip form writes, transforms per frame (1), whether a GEMM with the filter table follows}.  form 0: transform and
+ * descriptors (or Chroma's squared magnitudes) in one launch, a run of 32 frames per workgroup, the magnitudes stay in the
+ * LDS -- fft 1024, 2048 and 4096 with an even window.  form 1: the STFT launch leaves a round's magnitudes in a workspace,
+ * the kernels read them (run 0). */
+int fluhip_debug_spectral_plan(fluhip_ctx* ctx, int64_t fft, int64_t win, int kind, int64_t* out4);
 
 /* ---- feature pipeline: BufMelBands / BufMFCC (BASELINE config 5) ------------------------------ */
 /* Replaces, for `count` equal-length mono buffers at once, the offline-wrapped real-time clients

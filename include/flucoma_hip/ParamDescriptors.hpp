@@ -19,6 +19,7 @@
 //   rt/OnsetSliceClient.hpp:38-48, rt/OnsetFeatureClient.hpp:29-37 (tests/golden/param_descriptors_onset.json)
 //   rt/HPSSClient.hpp:37-48, :126-130 (tests/golden/param_descriptors_hpss.json)
 //   rt/PitchClient.hpp:39-48, :180-182 (tests/golden/param_descriptors_pitch.json)
+//   rt/SpectralShapeClient.hpp:39-47, :150-153, rt/ChromaClient.hpp:36-42, :138-140 (tests/golden/param_descriptors_spectral.json)
 //   rt/NMFFilterClient.hpp:34-38      rt/NMFMatchClient.hpp:32-38       (the two real-time clients behind the offline
 //                                                                        wrapper's parameters, as NMFFilterClient.hpp /
 //                                                                        NMFMatchClient.hpp here describe)
@@ -344,6 +345,45 @@ inline constexpr ParamDescriptor kBufPitch[] = {
     floatMinMaxRel("minFreq", "Low Frequency Bound", 20, 0, 10000, "UpperLimit<maxFreq>"),
     floatMinMaxRel("maxFreq", "High Frequency Bound", 10000, 1, 20000, "LowerLimit<minFreq>"),
     enumParam("unit", "Frequency Unit", 0, kPitchUnits),
+    fft("fftSettings", "FFT Settings", 1024, -1, -1)};
+
+inline constexpr const char* kShapeSelect[] = {"centroid", "spread", "skew", "kurtosis", "rolloff", "flatness", "crest"};
+inline constexpr const char* kShapeUnits[] = {"Hz", "Midi Cents"};
+
+// the control wrapper's parameters, then rt/SpectralShapeClient.hpp:39-47
+inline constexpr ParamDescriptor kBufSpectralShape[] = {
+    inputBuffer("source", "Source Buffer"),
+    longMin("startFrame", "Source Offset", 0, 0),
+    longParam("numFrames", "Number of Frames", -1),
+    longMin("startChan", "Start Channel", 0, 0),
+    longParam("numChans", "Number of Channels", -1),
+    buffer("features", "Features Buffer"),
+    enumParam("padding", "Added Padding", 1, kPaddingModes),
+    choices("select", "Selection of Features", kShapeSelect),
+    floatMin("minFreq", "Low Frequency Bound", 0, 0),
+    floatMin("maxFreq", "High Frequency Bound", -1, -1),
+    floatMinMax("rolloffPercent", "Rolloff Percent", 95, 0, 100),
+    enumParam("unit", "Frequency Unit", 0, kShapeUnits),
+    enumParam("power", "Use Power", 0, kNoYes),
+    fft("fftSettings", "FFT Settings", 1024, -1, -1)};
+
+inline constexpr const char* kChromaNormalize[] = {"None", "Sum", "Max"};
+
+// the control wrapper's parameters, then rt/ChromaClient.hpp:36-42.  (numChroma is LongParamRuntimeMax<Primary>: its runtime
+// maximum is a host attribute of the real-time object and has no offline meaning.)
+inline constexpr ParamDescriptor kBufChroma[] = {
+    inputBuffer("source", "Source Buffer"),
+    longMin("startFrame", "Source Offset", 0, 0),
+    longParam("numFrames", "Number of Frames", -1),
+    longMin("startChan", "Start Channel", 0, 0),
+    longParam("numChans", "Number of Channels", -1),
+    buffer("features", "Output Buffer"),
+    enumParam("padding", "Added Padding", 1, kPaddingModes),
+    longMin("numChroma", "Number of Chroma Bins per Octave", 12, 2),
+    floatMinMax("ref", "Reference frequency", 440, 0, 22000),
+    enumParam("normalize", "Normalize Frame", 0, kChromaNormalize),
+    floatMin("minFreq", "Low Frequency Bound", 0, 0),
+    floatMin("maxFreq", "High Frequency Bound", -1, -1),
     fft("fftSettings", "FFT Settings", 1024, -1, -1)};
 
 template <std::size_t N>

@@ -12,6 +12,7 @@ mirrors' tables (include/flucoma_hip/ParamDescriptors.hpp).  tests/test_client.p
     python tools/make_param_descriptor_fixture.py --onset [/root/reference] > tests/golden/param_descriptors_onset.json
     python tools/make_param_descriptor_fixture.py --hpss [/root/reference] > tests/golden/param_descriptors_hpss.json
     python tools/make_param_descriptor_fixture.py --pitch [/root/reference] > tests/golden/param_descriptors_pitch.json
+    python tools/make_param_descriptor_fixture.py --spectral [/root/reference] > tests/golden/param_descriptors_spectral.json
 
 Offline clients the reference composes with makeNRTParams (BufMFCC, BufMelBands: rt/MFCCClient.hpp:171-173,
 rt/MelBandsClient.hpp:151-153) get the wrapper's parameters in front exactly as FluidNRTClientWrapper.hpp:33-39, :747-785
@@ -246,6 +247,17 @@ def main_pitch():
     sys.stdout.write("\n")
 
 
+def main_spectral():
+    """--spectral: tests/golden/param_descriptors_spectral.json, BufSpectralShape and BufChroma (control wrapper)"""
+    win, pad = wrapper_inputs(), padding_param()
+    out = {}
+    for name, header in (("BufSpectralShape", "rt/SpectralShapeClient.hpp"), ("BufChroma", "rt/ChromaClient.hpp")):
+        bufs = nrt_buffers(header)
+        out[name] = [bufs[0]] + win + bufs[1:] + [pad] + table(header)
+    json.dump(out, sys.stdout, indent=1)
+    sys.stdout.write("\n")
+
+
 def main():
     win = wrapper_inputs()
     pad = padding_param()
@@ -274,5 +286,7 @@ if __name__ == "__main__":
         main_hpss()
     elif "--pitch" in sys.argv:
         main_pitch()
+    elif "--spectral" in sys.argv:
+        main_spectral()
     else:
         main()

@@ -288,6 +288,30 @@ def pitch_row(ctx, reps, count, seconds, algorithm):
                       "plan": ctx.pitch_plan(fft, win, algorithm)}}
 
 
+def spectral_row(ctx, reps, count, seconds, kind):
+    """BufSpectralShape (kind 0) or BufChroma (kind 1) at the client defaults (fft 1024, hop 512) from host buffers: host wall time
+    of the call, min of `reps`, next to the device time of its transform launch over the same frames (fluhip_prof_read class 0)"""
+    n, win, fft, hop = int(seconds * SR), 1024, 1024, 512
+    base = np.stack([synth.synth_audio(n, 1000 + b) for b in range(min(count, 16))]).astype(np.float32)
+    x = np.tile(base, (-(-count // len(base)), 1))[:count]
+    call = (lambda: ctx.bufspectralshape(x, win=win, fft=fft, hop=hop)) if kind == 0 else (lambda: ctx.bufchroma(x, win=win, fft=fft, hop=hop))
+    out = call(); ctx.synchronize()      # warm
+    wall, stft = [], []
+    ctx.prof_enable(True)
+    for _ in range(reps):
+        ctx.prof_reset()
+        t0 = time.perf_counter()
+        call()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        stft.append(ctx.prof_read(0)[1])
+    ctx.prof_enable(False)
+    name = "BufSpectralShape" if kind == 0 else "BufChroma"
+    return {"unit": f"ms per {name} call from host buffers (host wall time); stft_ms: its transform launch, device-timed",
+            "ms": stats(wall), "stft_ms": stats(stft),
+            "shape": {"buffers": count, "frames": int(out.shape[2]), "bins": fft // 2 + 1, "channels": int(out.shape[1]),
+                      "plan": ctx.spectral_plan(fft, win, kind)}}
+
+
 def client_row(driver, reps, tmp):
     """the 8-channel x 10 s rank-32 BufNMF job through the C++17 host client (wall time of process(): host timed by necessity
     -- it is a host-side job: gather, upload, 200 iterations, write-back -- min of `reps`)"""
@@ -407,6 +431,8 @@ def main():
     put("pitch_8192x2s_yin", lambda: pitch_row(ctx, R, 8192 // q, 2, 2))
     put("pitch_8192x2s_cepstrum", lambda: pitch_row(ctx, R, 8192 // q, 2, 0))
     put("pitch_1x600s_hps", lambda: pitch_row(ctx, R, 1, 600 // q, 1))
+    put("spectralshape_8192x2s", lambda: spectral_row(ctx, R, 8192 // q, 2, 0))
+    put("chroma_8192x2s", lambda: spectral_row(ctx, R, 8192 // q, 2, 1))
     put("c3_2x10min_k128_fft4096", lambda: corpus_row(ctx, 2, 600, 128, 40 // min(q, 4), max(3, R - 2), win=4096, fft=4096, hop=1024, tile=441000))
     if want("client_8ch_10s_k32"):
         import importlib.util
