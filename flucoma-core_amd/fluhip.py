@@ -76,6 +76,7 @@ EXPORTS = [
     "fluhip_pitch_frames_f64", "fluhip_debug_pitch_curve_f64", "fluhip_bufpitch_f32", "fluhip_debug_pitch_plan",
     "fluhip_spectralshape_frames_f64", "fluhip_bufspectralshape_f32", "fluhip_debug_chroma_filters_f64",
     "fluhip_chroma_frames_f64", "fluhip_bufchroma_f32", "fluhip_debug_spectral_plan",
+    "fluhip_loudness_frames_f64", "fluhip_bufloudness_f32", "fluhip_debug_loudness_plan",
     "fluhip_debug_features_plan", "fluhip_debug_resynth_f64", "fluhip_debug_corpus_read_layouts_f64",
 ]
 
@@ -177,6 +178,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.fluhip_bufchroma_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, _i64, _dbl, ctypes.c_int, _dbl,
                                        _dbl, _dbl, _fp, _ip]
     L.fluhip_debug_spectral_plan.argtypes = [_vp, _i64, _i64, ctypes.c_int, _ip]
+    L.fluhip_loudness_frames_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _dbl, _dp]
+    L.fluhip_bufloudness_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         _dbl, _fp, _ip]
+    L.fluhip_debug_loudness_plan.argtypes = [_vp, _i64, _i64, _dbl, _ip]
     L.fluhip_debug_features_plan.argtypes = [_vp, ctypes.c_int, _i64, _i64, _i64, _i64, _i64, _dbl, _dbl, _dbl, _ip]
     L.fluhip_corpus_create.argtypes = [_vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
     L.fluhip_corpus_create_ragged.argtypes = [_vp, _i64, _ip, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
@@ -896,6 +901,36 @@ class Context:
         form 1: two passes through a magnitude workspace (run 0)"""
         out = (_i64 * 4)()
         self._check(self.lib.fluhip_debug_spectral_plan(self.h, fft, win, kind, out))
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    # ---- BufLoudness (algorithms/public/Loudness.hpp, util/KWeightingFilter.hpp, util/TruePeak.hpp and the client) -----------
+    def loudness_frames(self, x, win=1024, hop=512, k_weighting=1, true_peak=1, sample_rate=44100.0):
+        """Loudness::processFrame over the frames x[j hop : j hop + win] of signals [count,n] (or [n]), the filter and the
+        interpolator carried from frame 0 -> [count,T,2] doubles (loudness, peak), T = 1 + (n - win) // hop"""
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+        count, n = x.shape
+        T = 1 + (n - win) // hop if (n >= win and hop >= 1 and win >= 1) else 0
+        out = np.empty((count, max(T, 0), 2))
+        self._check(self.lib.fluhip_loudness_frames_f64(self.h, _d(x), count, n, win, hop, k_weighting, true_peak, sample_rate,
+                                                        _d(out)))
+        return out
+
+    def bufloudness(self, audio, select=3, k_weighting=1, true_peak=1, win=1024, hop=512, padding_mode=1, sample_rate=44100.0):
+        """NRTLoudnessClient on mono buffers [count,n] (or [n]) -> float32 [count,selected,frames]"""
+        audio = np.ascontiguousarray(np.atleast_2d(audio), dtype=np.float32)
+        count, n = audio.shape
+        Tr = _i64(0)
+        args = (win, hop, padding_mode, select, k_weighting, true_peak, sample_rate)
+        self._check(self.lib.fluhip_bufloudness_f32(self.h, _f(audio), count, n, *args, None, ctypes.byref(Tr)))
+        out = np.empty((count, bin(select & 3).count("1"), Tr.value), dtype=np.float32)
+        self._check(self.lib.fluhip_bufloudness_f32(self.h, _f(audio), count, n, *args, _f(out), ctypes.byref(Tr)))
+        return out
+
+    def loudness_plan(self, win, hop, sample_rate=44100.0):
+        """(form, frames a workgroup owns, interpolation factor 4 / 2 / 1, history samples the interpolator reads in front of
+        a frame); form 0: lane = frame, the filter states by a double-double scan per buffer"""
+        out = (_i64 * 4)()
+        self._check(self.lib.fluhip_debug_loudness_plan(self.h, win, hop, sample_rate, out))
         return int(out[0]), int(out[1]), int(out[2]), int(out[3])
 
     # ---- profiling ----------------------------------------------------------------------

@@ -39,7 +39,8 @@ extern "C" {
  * fluhip_debug_features_plan, fluhip_hpss_planes_f64, fluhip_bufhpss_f32, fluhip_debug_hpss_plan, fluhip_pitch_frames_f64,
  * fluhip_debug_pitch_curve_f64, fluhip_bufpitch_f32, fluhip_debug_pitch_plan, fluhip_debug_resynth_f64,
  * fluhip_debug_corpus_read_layouts_f64, fluhip_spectralshape_frames_f64, fluhip_bufspectralshape_f32,
- * fluhip_debug_chroma_filters_f64, fluhip_chroma_frames_f64, fluhip_bufchroma_f32, fluhip_debug_spectral_plan. */
+ * fluhip_debug_chroma_filters_f64, fluhip_chroma_frames_f64, fluhip_bufchroma_f32, fluhip_debug_spectral_plan,
+ * fluhip_loudness_frames_f64, fluhip_bufloudness_f32, fluhip_debug_loudness_plan. */
 #define FLUHIP_ABI_VERSION 5
 
 /* clients/common/Result.hpp:24  enum class Status { kOk, kWarning, kError, kCancelled } */
@@ -534,6 +535,36 @@ int fluhip_bufchroma_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int
  * LDS -- fft 1024, 2048 and 4096 with an even window.  form 1: the STFT launch leaves a round's magnitudes in a workspace,
  * the kernels read them (run 0). */
 int fluhip_debug_spectral_plan(fluhip_ctx* ctx, int64_t fft, int64_t win, int kind, int64_t* out4);
+
+/* ---- BufLoudness (clients/rt/LoudnessClient.hpp) ---------------------------------------------------------- */
+/* algorithm::Loudness::processFrame (algorithms/public/Loudness.hpp:43-61) on the frames of `count` signals: x count x n
+ * doubles (host), frame j = x[j hop .. j hop + win), T = 1 + (n - win) / hop frames per signal, out count x T x 2 doubles
+ * (host): loudness = -0.691 + 10 log10(mean(filtered^2) + epsilon) and peak = 20 log10(peak + epsilon), epsilon DBL_EPSILON.
+ * One Loudness object per signal, initialised once: the K-weighting filter (util/KWeightingFilter.hpp, the shelving and the
+ * high-pass biquad as one 5-tap direct-form-I recursion, coefficients in double from the sample rate) is never reset between
+ * frames, and the true-peak interpolator (util/TruePeak.hpp: 49 taps, Hann-windowed sinc, factor 4 below 88200 Hz, 2 from
+ * there on, taps with |c| <= 1e-6 dropped) keeps its ring buffer of ceil(49 / factor) samples: both states are carried from
+ * frame 0 through the overlapping frames, nothing is dropped.  The -0.691 stays when k_weighting is 0; the peak is taken from
+ * the unfiltered frame; at 176400 Hz and above, and with true_peak 0, it is max |x|.  No state passes between signals: a
+ * batch gives the bits of single calls.  hop > win is legal.
+ * Errors: win outside [1, 32768], hop < 1, k_weighting / true_peak outside {0, 1}, a sample rate that is not positive and
+ * finite, count < 1, n < win ("not enough frames"); nothing is written. */
+int fluhip_loudness_frames_f64(fluhip_ctx* ctx, const double* x, int64_t count, int64_t n, int64_t win, int64_t hop, int k_weighting,
+                               int true_peak, double sample_rate, double* out);
+/* NRTLoudnessClient (LoudnessClient behind StreamingControl, clients/common/FluidNRTClientWrapper.hpp:551-660) for `count`
+ * equal-length mono buffers of n float samples: padding_mode 0 None, 1 Default (win / 2), 2 Full (win - hop); the latency is
+ * win; analysis frame j holds the win samples from j hop - win - padding of the input on (zeros outside it); every frame,
+ * the latency frames included, runs through the filter and the interpolator, then the first win / hop results are dropped.
+ * select bit 0 loudness, bit 1 peak; out count x selected x frames floats (host), *frames_out the kept frames; out NULL is the
+ * size query.  Errors: as above, select outside [1, 3], padding_mode outside {0, 1, 2}, padding_mode 2 with hop > win (the
+ * reference copies its input to a negative offset), no frame left. */
+int fluhip_bufloudness_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t n, int64_t win, int64_t hop, int padding_mode,
+                           int select, int k_weighting, int true_peak, double sample_rate, float* out, int64_t* frames_out);
+/* Diagnostic: how (win, hop, sample rate) is computed: out4 = {form, frames a workgroup owns, interpolation factor (4 / 2 /
+ * 1 = no interpolator), history samples of the frame stream the interpolator reads in front of a frame (ring - 1)}.  form 0:
+ * lane = frame -- zero-state end states, a scan of 8-value states per buffer in double-double, every frame run again from its
+ * entering state.  ctx may be NULL (an error then leaves no message). */
+int fluhip_debug_loudness_plan(fluhip_ctx* ctx, int64_t win, int64_t hop, double sample_rate, int64_t* out4);
 
 /* ---- feature pipeline: BufMelBands / BufMFCC (BASELINE config 5) ------------------------------ */
 /* Replaces, for `count` equal-length mono buffers at once, the offline-wrapped real-time clients

@@ -20,6 +20,7 @@
 //   rt/HPSSClient.hpp:37-48, :126-130 (tests/golden/param_descriptors_hpss.json)
 //   rt/PitchClient.hpp:39-48, :180-182 (tests/golden/param_descriptors_pitch.json)
 //   rt/SpectralShapeClient.hpp:39-47, :150-153, rt/ChromaClient.hpp:36-42, :138-140 (tests/golden/param_descriptors_spectral.json)
+//   rt/LoudnessClient.hpp:36-45, :144-146 (tests/golden/param_descriptors_loudness.json)
 //   rt/NMFFilterClient.hpp:34-38      rt/NMFMatchClient.hpp:32-38       (the two real-time clients behind the offline
 //                                                                        wrapper's parameters, as NMFFilterClient.hpp /
 //                                                                        NMFMatchClient.hpp here describe)
@@ -48,6 +49,7 @@ struct ParamDescriptor
   const char*        relational;    // constraints against other parameters, as the reference spells them, or nullptr
   const double*      pairsDefault;  // FloatPairsArray: the fixedSize default values (x1, y1, x2, y2), else nullptr
   int                fixedSize;     // FloatPairsArray: 4 (cc/ParameterTypes.hpp:256), else 0
+  bool               fixed = false; // LongParam<Fixed<true>>: set when the object is made, not afterwards
 };
 
 struct ParamDescriptorList
@@ -81,6 +83,11 @@ constexpr ParamDescriptor longMin(const char* n, const char* d, double def, doub
 constexpr ParamDescriptor longMinMax(const char* n, const char* d, double def, double lo, double hi)
 {
   return {n, d, ParamKind::kLong, def, true, lo, true, hi, nullptr, 0, 0, 0, nullptr, nullptr, 0};
+}
+// a Fixed<true> parameter with both bounds and constraints spelled as the reference has them
+constexpr ParamDescriptor longFixedMinMax(const char* n, const char* d, double def, double lo, double hi, const char* rel)
+{
+  return {n, d, ParamKind::kLong, def, true, lo, true, hi, nullptr, 0, 0, 0, rel, nullptr, 0, true};
 }
 constexpr ParamDescriptor floatMin(const char* n, const char* d, double def, double lo)
 {
@@ -385,6 +392,25 @@ inline constexpr ParamDescriptor kBufChroma[] = {
     floatMin("minFreq", "Low Frequency Bound", 0, 0),
     floatMin("maxFreq", "High Frequency Bound", -1, -1),
     fft("fftSettings", "FFT Settings", 1024, -1, -1)};
+
+inline constexpr const char* kLoudnessSelect[] = {"loudness", "peak"};
+inline constexpr const char* kOffOn[] = {"Off", "On"};
+
+// the control wrapper's parameters, then rt/LoudnessClient.hpp:36-45
+inline constexpr ParamDescriptor kBufLoudness[] = {
+    inputBuffer("source", "Source Buffer"),
+    longMin("startFrame", "Source Offset", 0, 0),
+    longParam("numFrames", "Number of Frames", -1),
+    longMin("startChan", "Start Channel", 0, 0),
+    longParam("numChans", "Number of Channels", -1),
+    buffer("features", "Features Buffer"),
+    enumParam("padding", "Added Padding", 1, kPaddingModes),
+    choices("select", "Selection of Outputs", kLoudnessSelect),
+    enumParam("kWeighting", "Apply K-Weighting", 1, kOffOn),
+    enumParam("truePeak", "Compute True Peak", 1, kOffOn),
+    longMin("windowSize", "Window Size", 1024, 1, "UpperLimit<maxWindowSize>"),
+    longMin("hopSize", "Hop Size", 512, 1),
+    longFixedMinMax("maxWindowSize", "Max Window Size", 16384, 4, 32768, "PowerOfTwo")};
 
 template <std::size_t N>
 constexpr ParamDescriptorList list(const ParamDescriptor (&a)[N])

@@ -13,6 +13,7 @@ mirrors' tables (include/flucoma_hip/ParamDescriptors.hpp).  tests/test_client.p
     python tools/make_param_descriptor_fixture.py --hpss [/root/reference] > tests/golden/param_descriptors_hpss.json
     python tools/make_param_descriptor_fixture.py --pitch [/root/reference] > tests/golden/param_descriptors_pitch.json
     python tools/make_param_descriptor_fixture.py --spectral [/root/reference] > tests/golden/param_descriptors_spectral.json
+    python tools/make_param_descriptor_fixture.py --loudness [/root/reference] > tests/golden/param_descriptors_loudness.json
 
 Offline clients the reference composes with makeNRTParams (BufMFCC, BufMelBands: rt/MFCCClient.hpp:171-173,
 rt/MelBandsClient.hpp:151-153) get the wrapper's parameters in front exactly as FluidNRTClientWrapper.hpp:33-39, :747-785
@@ -258,6 +259,25 @@ def main_spectral():
     sys.stdout.write("\n")
 
 
+def fixed_names(header):
+    """the names of the parameters a header declares Fixed<true> (set when the object is made)"""
+    text = strip_comments(open(os.path.join(INC, header)).read())
+    return set(re.findall(r'\w+\s*<\s*Fixed\s*<\s*true\s*>\s*>\s*\(\s*"(\w+)"', text))
+
+
+def main_loudness():
+    """--loudness: tests/golden/param_descriptors_loudness.json, BufLoudness (control wrapper); its maxWindowSize carries
+    "fixed": true"""
+    header = "rt/LoudnessClient.hpp"
+    bufs = nrt_buffers(header)
+    tab = table(header)
+    for d in tab:
+        if d["name"] in fixed_names(header):
+            d["fixed"] = True
+    json.dump({"BufLoudness": [bufs[0]] + wrapper_inputs() + bufs[1:] + [padding_param()] + tab}, sys.stdout, indent=1)
+    sys.stdout.write("\n")
+
+
 def main():
     win = wrapper_inputs()
     pad = padding_param()
@@ -288,5 +308,7 @@ if __name__ == "__main__":
         main_pitch()
     elif "--spectral" in sys.argv:
         main_spectral()
+    elif "--loudness" in sys.argv:
+        main_loudness()
     else:
         main()
