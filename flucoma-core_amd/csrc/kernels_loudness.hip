@@ -23,6 +23,7 @@
 // run (chunk + 1) 8 bytes whatever the window.  The kernels take run and chunk from the launch: nothing assumes them.
 // Every order of operations depends on (win, hop, the frame's position in its buffer) alone, so a batch gives the bits of
 // single calls.  Compiled with -ffp-contract=off (the double-double arithmetic needs each rounding) and no fast-math flag.
+#include "fluhip_dd.h"
 #include "fluhip_kernels.h"
 #include "fluhip_loudness.h"
 
@@ -121,39 +122,7 @@ __global__ __launch_bounds__(256) void loudness_filter_kernel(LoudnessFrames p, 
   }
 }
 
-// ---- double-double (an unevaluated sum hi + lo, |lo| <= ulp(hi) / 2) -----------------------------------------------------------
-struct dd
-{
-  double hi, lo;
-};
-__host__ __device__ __forceinline__ dd quick_two_sum(double a, double b)
-{
-  const double s = a + b;
-  return {s, b - (s - a)};
-}
-__host__ __device__ __forceinline__ dd two_sum(double a, double b)
-{
-  const double s = a + b;
-  const double bb = s - a;
-  return {s, (a - (s - bb)) + (b - bb)};
-}
-__host__ __device__ __forceinline__ dd dd_add(dd a, dd b)
-{
-  dd s = two_sum(a.hi, b.hi);
-  const dd t = two_sum(a.lo, b.lo);
-  s.lo += t.hi;
-  s = quick_two_sum(s.hi, s.lo);
-  s.lo += t.lo;
-  return quick_two_sum(s.hi, s.lo);
-}
-__host__ __device__ __forceinline__ dd dd_mul(dd a, dd b)
-{
-  const double p = a.hi * b.hi;
-  double e = fma(a.hi, b.hi, -p);
-  e += a.hi * b.lo + a.lo * b.hi;
-  return quick_two_sum(p, e);
-}
-
+// (the double-double arithmetic of the scan and of frame_transition is in fluhip_dd.h)
 // lane i of a group of 8 owns row i of M and entry i of the state of its buffer
 __global__ __launch_bounds__(64) void loudness_scan_kernel(const double* q, int64_t B, int64_t T, LoudnessTransition M, double* st)
 {

@@ -77,6 +77,8 @@ EXPORTS = [
     "fluhip_spectralshape_frames_f64", "fluhip_bufspectralshape_f32", "fluhip_debug_chroma_filters_f64",
     "fluhip_chroma_frames_f64", "fluhip_bufchroma_f32", "fluhip_debug_spectral_plan",
     "fluhip_loudness_frames_f64", "fluhip_bufloudness_f32", "fluhip_debug_loudness_plan",
+    "fluhip_amp_envelope_f64", "fluhip_amp_slices_f64", "fluhip_bufampslice_f32", "fluhip_bufampfeature_f32",
+    "fluhip_debug_amp_plan",
     "fluhip_debug_features_plan", "fluhip_debug_resynth_f64", "fluhip_debug_corpus_read_layouts_f64",
 ]
 
@@ -182,6 +184,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.fluhip_bufloudness_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          _dbl, _fp, _ip]
     L.fluhip_debug_loudness_plan.argtypes = [_vp, _i64, _i64, _dbl, _ip]
+    L.fluhip_amp_envelope_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _dbl, _dbl, _dp]
+    L.fluhip_amp_slices_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _dbl, _dbl, _dbl, _i64, _dbl,
+                                        _u8p, _ip, _dp]
+    L.fluhip_bufampslice_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _dbl, _dbl, _dbl, _i64, _dbl,
+                                         _dbl, _ip, _i64, _ip]
+    L.fluhip_bufampfeature_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _dbl, _dbl, _dbl, _fp]
+    L.fluhip_debug_amp_plan.argtypes = [_vp, _dbl, _ip]
     L.fluhip_debug_features_plan.argtypes = [_vp, ctypes.c_int, _i64, _i64, _i64, _i64, _i64, _dbl, _dbl, _dbl, _ip]
     L.fluhip_corpus_create.argtypes = [_vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
     L.fluhip_corpus_create_ragged.argtypes = [_vp, _i64, _ip, _i64, _i64, _i64, _i64, ctypes.POINTER(_vp)]
@@ -931,6 +940,69 @@ class Context:
         a frame); form 0: lane = frame, the filter states by a double-double scan per buffer"""
         out = (_i64 * 4)()
         self._check(self.lib.fluhip_debug_loudness_plan(self.h, win, hop, sample_rate, out))
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    # ---- BufAmpSlice / BufAmpFeature (algorithms/public/Envelope.hpp, EnvelopeSegmentation.hpp and the two clients) ---------
+    def amp_envelope(self, x, fast_up=1, fast_down=1, slow_up=100, slow_down=100, floor=-144.0, hipass=0.0):
+        """Envelope::processSample over signals [count,n] (or [n]) of doubles, hipass the cutoff as a fraction of the sample
+        rate -> [count,n] doubles"""
+        x, count, n, ld = self._onset_signal(x)
+        out = np.empty((count, n))
+        self._check(self.lib.fluhip_amp_envelope_f64(self.h, x.ctypes.data_as(_dp), count, n, ld, fast_up, fast_down, slow_up,
+                                                     slow_down, floor, hipass, _d(out)))
+        return out
+
+    def amp_slices(self, x, fast_up=1, fast_down=1, slow_up=100, slow_down=100, on=144.0, off=-144.0, floor=-144.0, min_slice=2,
+                   hipass=0.0, want_det=True, want_envelope=True):
+        """EnvelopeSegmentation::processSample over signals [count,n] (or [n]) -> (det [count,n] uint8 or None, counts [count],
+        envelope [count,n] or None)"""
+        x, count, n, ld = self._onset_signal(x)
+        det = np.empty((count, n), dtype=np.uint8) if want_det else None
+        env = np.empty((count, n)) if want_envelope else None
+        counts = np.empty(count, dtype=np.int64)
+        self._check(self.lib.fluhip_amp_slices_f64(self.h, x.ctypes.data_as(_dp), count, n, ld, fast_up, fast_down, slow_up,
+                                                   slow_down, on, off, floor, min_slice, hipass,
+                                                   det.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if want_det else None,
+                                                   counts.ctypes.data_as(_ip), _d(env)))
+        return det, counts, env
+
+    def bufampslice(self, audio, fast_up=1, fast_down=1, slow_up=100, slow_down=100, on=144.0, off=-144.0, floor=-144.0,
+                    min_slice=2, high_pass_freq=85.0, sample_rate=44100.0, start_frame=0, capacity=None):
+        """NRTAmpSliceClient on audio [count,channels,n] (or [channels,n] / [n]): a list of int64 index arrays, one per buffer
+        ([-1] when nothing was detected).  capacity: values kept per buffer (default: every possible one)"""
+        audio = np.asarray(audio, dtype=np.float32)
+        while audio.ndim < 3:
+            audio = audio[None]
+        audio = np.ascontiguousarray(audio)
+        count, channels, n = audio.shape
+        if capacity is None:
+            capacity = n // 2 + 2   # a detection needs the previous value below the threshold: every other sample at most
+        idx = np.full((count, max(capacity, 1)), -2, dtype=np.int64)
+        counts = np.zeros(count, dtype=np.int64)
+        self._check(self.lib.fluhip_bufampslice_f32(self.h, _f(audio), count, channels, n, start_frame, fast_up, fast_down,
+                                                    slow_up, slow_down, on, off, floor, min_slice, high_pass_freq, sample_rate,
+                                                    idx.ctypes.data_as(_ip), capacity, counts.ctypes.data_as(_ip)))
+        self.last_slice_counts = counts
+        return [idx[b, :min(int(counts[b]), capacity)].copy() for b in range(count)]
+
+    def bufampfeature(self, audio, fast_up=1, fast_down=1, slow_up=100, slow_down=100, floor=-144.0, high_pass_freq=85.0,
+                      sample_rate=44100.0):
+        """NRTAmpFeatureClient on audio [count,channels,n] (or [channels,n] / [n]) -> float32 [count,channels,n]"""
+        audio = np.asarray(audio, dtype=np.float32)
+        while audio.ndim < 3:
+            audio = audio[None]
+        audio = np.ascontiguousarray(audio)
+        count, channels, n = audio.shape
+        out = np.empty((count, channels, n), dtype=np.float32)
+        self._check(self.lib.fluhip_bufampfeature_f32(self.h, _f(audio), count, channels, n, fast_up, fast_down, slow_up,
+                                                      slow_down, floor, high_pass_freq, sample_rate, _f(out)))
+        return out
+
+    def amp_plan(self, hipass=85.0 / 44100.0):
+        """(form, samples of a front-end chunk, signals per wavefront of the serial follower kernel, 1 if the high-pass scan
+        launches run)"""
+        out = (_i64 * 4)()
+        self._check(self.lib.fluhip_debug_amp_plan(self.h, hipass, out))
         return int(out[0]), int(out[1]), int(out[2]), int(out[3])
 
     # ---- profiling ----------------------------------------------------------------------

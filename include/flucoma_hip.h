@@ -40,7 +40,8 @@ extern "C" {
  * fluhip_debug_pitch_curve_f64, fluhip_bufpitch_f32, fluhip_debug_pitch_plan, fluhip_debug_resynth_f64,
  * fluhip_debug_corpus_read_layouts_f64, fluhip_spectralshape_frames_f64, fluhip_bufspectralshape_f32,
  * fluhip_debug_chroma_filters_f64, fluhip_chroma_frames_f64, fluhip_bufchroma_f32, fluhip_debug_spectral_plan,
- * fluhip_loudness_frames_f64, fluhip_bufloudness_f32, fluhip_debug_loudness_plan. */
+ * fluhip_loudness_frames_f64, fluhip_bufloudness_f32, fluhip_debug_loudness_plan, fluhip_amp_envelope_f64,
+ * fluhip_amp_slices_f64, fluhip_bufampslice_f32, fluhip_bufampfeature_f32, fluhip_debug_amp_plan. */
 #define FLUHIP_ABI_VERSION 5
 
 /* clients/common/Result.hpp:24  enum class Status { kOk, kWarning, kError, kCancelled } */
@@ -565,6 +566,54 @@ int fluhip_bufloudness_f32(fluhip_ctx* ctx, const float* audio, int64_t count, i
  * lane = frame -- zero-state end states, a scan of 8-value states per buffer in double-double, every frame run again from its
  * entering state.  ctx may be NULL (an error then leaves no message). */
 int fluhip_debug_loudness_plan(fluhip_ctx* ctx, int64_t win, int64_t hop, double sample_rate, int64_t* out4);
+
+/* ---- BufAmpSlice / BufAmpFeature (clients/rt/AmpSliceClient.hpp, AmpFeatureClient.hpp) ---------------------- */
+/* Added within version 5 (additive).  FP64 throughout, every signal of a call in the same launches; there are no frames:
+ * every sample depends on the one before.
+ * algorithm::Envelope::processSample (algorithms/public/Envelope.hpp:36-61) over `count` signals: x count x n doubles
+ * (host), rows ld apart; out count x n doubles (host).  One Envelope object per signal, initialised once.  Per sample: a
+ * sample that is not finite is replaced by the last finite one (0 before the first); two identical second-order Butterworth
+ * high-pass sections in cascade (util/ButterworthHPFilter.hpp: direct form I, zero initial state, coefficients in double from
+ * hipass = the cutoff as a fraction of the sample rate, the recursion evaluated left to right; hipass 0 bypasses them);
+ * 20 log10 |.|, then max(., floor_db) (a zero gives -inf, which becomes the floor); two SlideUDFilters (util/
+ * SlideUDFilter.hpp) that both start at floor_db, take 1 / ramp_up when the input is strictly above their state and
+ * 1 / ramp_down otherwise, and move by y0 + (b * (x - y0)) in three roundings; the value is fast - slow.
+ * The front end up to the clipped level is computed in chunks of 1024 samples whose entering filter states come from a scan
+ * (carried in double-double), every chunk then run in plain double in the reference's order; the followers run serially, a
+ * lane pair per signal.  Nothing depends on count or on n: a batch gives the bits of single calls.
+ * Errors: a ramp below 1, floor_db outside [-144, 144], hipass outside [0, 0.5], count < 1, n < 1, ld < n; the message names
+ * the parameter, nothing is clamped and nothing is written. */
+int fluhip_amp_envelope_f64(fluhip_ctx* ctx, const double* x, int64_t count, int64_t n, int64_t ld, int64_t fast_up,
+                            int64_t fast_down, int64_t slow_up, int64_t slow_down, double floor_db, double hipass, double* out);
+/* algorithm::EnvelopeSegmentation::processSample (algorithms/public/EnvelopeSegmentation.hpp:36-60) over the same envelope:
+ * det count x n bytes (host, may be NULL), 1 where a slice starts; counts (count) how many; envelope count x n doubles (may
+ * be NULL).  The previous value starts at 0; a detection needs !state && value > on && previous < on && debounce == 0, all
+ * strict; it sets the debounce counter to min_slice (0 is legal), and the counter is lowered only on samples that do not
+ * detect; state falls when value < off, tested after the detection on the same sample.
+ * Errors: as above, on / off outside [-144, 144], min_slice < 0. */
+int fluhip_amp_slices_f64(fluhip_ctx* ctx, const double* x, int64_t count, int64_t n, int64_t ld, int64_t fast_up, int64_t fast_down,
+                          int64_t slow_up, int64_t slow_down, double on, double off, double floor_db, int64_t min_slice,
+                          double hipass, unsigned char* det, int64_t* counts, double* envelope);
+/* NRTAmpSliceClient (AmpSliceClient behind NRTSliceAdaptor, clients/common/FluidNRTClientWrapper.hpp:665-725) for `count`
+ * buffers of `channels` x n float samples: the channels are summed in float, in channel order, starting from 0; hipass =
+ * min(high_pass_freq / sample_rate, 0.5); the client's latency is 0, so no detection is moved or merged at the front, and the
+ * zeros that fill the last host vector lie past n.  indices / capacity / counts / start_frame as fluhip_bufonsetslice_f32: at
+ * most `capacity` values per buffer (start_frame added) at indices + b * capacity, counts[b] the true number; a buffer without
+ * detection yields the single value -1.
+ * Errors: as above, a negative or non-finite high_pass_freq, a sample rate that is not positive and finite, channels < 1. */
+int fluhip_bufampslice_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t channels, int64_t n, int64_t start_frame,
+                           int64_t fast_up, int64_t fast_down, int64_t slow_up, int64_t slow_down, double on, double off,
+                           double floor_db, int64_t min_slice, double high_pass_freq, double sample_rate, int64_t* indices,
+                           int64_t capacity, int64_t* counts);
+/* NRTAmpFeatureClient (AmpFeatureClient behind NRTStreamAdaptor, FluidNRTClientWrapper.hpp:466-548): every channel on its own
+ * through a reset client, latency 0; out count x channels x n floats (host), each value cast to float. */
+int fluhip_bufampfeature_f32(fluhip_ctx* ctx, const float* audio, int64_t count, int64_t channels, int64_t n, int64_t fast_up,
+                             int64_t fast_down, int64_t slow_up, int64_t slow_down, double floor_db, double high_pass_freq,
+                             double sample_rate, float* out);
+/* Diagnostic: how the envelope is computed at hipass -- nothing else enters: out4 = {form, samples of a front-end chunk,
+ * signals per wavefront of the serial follower kernel, 1 if the high-pass scan launches run (hipass > 0)}.  form 0: lane =
+ * chunk in the front end, a lane pair per signal behind it.  ctx may be NULL (an error then leaves no message). */
+int fluhip_debug_amp_plan(fluhip_ctx* ctx, double hipass, int64_t* out4);
 
 /* ---- feature pipeline: BufMelBands / BufMFCC (BASELINE config 5) ------------------------------ */
 /* Replaces, for `count` equal-length mono buffers at once, the offline-wrapped real-time clients

@@ -21,6 +21,7 @@
 //   rt/PitchClient.hpp:39-48, :180-182 (tests/golden/param_descriptors_pitch.json)
 //   rt/SpectralShapeClient.hpp:39-47, :150-153, rt/ChromaClient.hpp:36-42, :138-140 (tests/golden/param_descriptors_spectral.json)
 //   rt/LoudnessClient.hpp:36-45, :144-146 (tests/golden/param_descriptors_loudness.json)
+//   rt/AmpSliceClient.hpp:39-48, :112-114, rt/AmpFeatureClient.hpp:36-42, :108-111 (tests/golden/param_descriptors_amp.json)
 //   rt/NMFFilterClient.hpp:34-38      rt/NMFMatchClient.hpp:32-38       (the two real-time clients behind the offline
 //                                                                        wrapper's parameters, as NMFFilterClient.hpp /
 //                                                                        NMFMatchClient.hpp here describe)
@@ -411,6 +412,39 @@ inline constexpr ParamDescriptor kBufLoudness[] = {
     longMin("windowSize", "Window Size", 1024, 1, "UpperLimit<maxWindowSize>"),
     longMin("hopSize", "Hop Size", 512, 1),
     longFixedMinMax("maxWindowSize", "Max Window Size", 16384, 4, 32768, "PowerOfTwo")};
+
+// the slicing wrapper's parameters and "indices", then rt/AmpSliceClient.hpp:39-48
+inline constexpr ParamDescriptor kBufAmpSlice[] = {
+    inputBuffer("source", "Source Buffer"),
+    longMin("startFrame", "Source Offset", 0, 0),
+    longParam("numFrames", "Number of Frames", -1),
+    longMin("startChan", "Start Channel", 0, 0),
+    longParam("numChans", "Number of Channels", -1),
+    buffer("indices", "Indices Buffer"),
+    longMin("fastRampUp", "Fast Envelope Ramp Up Length", 1, 1),
+    longMin("fastRampDown", "Fast Envelope Ramp Down Length", 1, 1),
+    longMin("slowRampUp", "Slow Envelope Ramp Up Length", 100, 1),
+    longMin("slowRampDown", "Slow Envelope Ramp Down Length", 100, 1),
+    floatMinMax("onThreshold", "On Threshold (dB)", 144, -144, 144),
+    floatMinMax("offThreshold", "Off Threshold (dB)", -144, -144, 144),
+    floatMinMax("floor", "Floor value (dB)", -144, -144, 144),
+    longMin("minSliceLength", "Minimum Length of Slice", 2, 0),
+    floatMin("highPassFreq", "High-Pass Filter Cutoff", 85, 0)};
+
+// the audio wrapper's parameters (no padding) and "features", then rt/AmpFeatureClient.hpp:36-42
+inline constexpr ParamDescriptor kBufAmpFeature[] = {
+    inputBuffer("source", "Source Buffer"),
+    longMin("startFrame", "Source Offset", 0, 0),
+    longParam("numFrames", "Number of Frames", -1),
+    longMin("startChan", "Start Channel", 0, 0),
+    longParam("numChans", "Number of Channels", -1),
+    buffer("features", "Feature Buffer"),
+    longMin("fastRampUp", "Fast Envelope Ramp Up Length", 1, 1),
+    longMin("fastRampDown", "Fast Envelope Ramp Down Length", 1, 1),
+    longMin("slowRampUp", "Slow Envelope Ramp Up Length", 100, 1),
+    longMin("slowRampDown", "Slow Envelope Ramp Down Length", 100, 1),
+    floatMinMax("floor", "Floor value (dB)", -144, -144, 144),
+    floatMin("highPassFreq", "High-Pass Filter Cutoff", 85, 0)};
 
 template <std::size_t N>
 constexpr ParamDescriptorList list(const ParamDescriptor (&a)[N])

@@ -1,0 +1,72 @@
+"""Device time of BufAmpSlice / BufAmpFeature at the client defaults (ramps 1 / 1 / 100 / 100, highPassFreq 85), for DESIGN K15.
+
+    python tools/amp_time.py [--reps 5] [--shapes 1x10,128x10,8192x2] [--high-pass 85] [--feature]
+
+Not a test: nothing in `pytest -m gpu` depends on a clock.  Each shape is `count` mono buffers of `seconds` at 44100 Hz from
+host float32 buffers through fluhip_bufampslice_f32 (or, with --feature, fluhip_bufampfeature_f32).  The figure is the device
+time of the call's kernel launches -- the hold pass, the zero-state pass, the scan, the level pass and the serial follower
+kernel of every round, bracketed by HIP events on the context stream (fluhip_prof_read, class 2) -- the minimum of `reps`
+calls; the host wall time of the whole call (uploads and the copy back included) stands beside it.  `serial_steps_per_buffer`
+is the length of the dependent chain no launch can cut: one follower step per sample.  --high-pass 0 times the form without
+the scan launches.  Prints one JSON line per shape.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "flucoma-core_amd"))
+import fluhip  # noqa: E402
+import synth  # noqa: E402
+
+SR = 44100
+
+
+def row(ctx, count, seconds, reps, high_pass, feature):
+    n = int(seconds * SR)
+    base = np.stack([synth.synth_audio(n, 1000 + b) for b in range(min(count, 16))]).astype(np.float32)
+    x = np.tile(base, (-(-count // len(base)), 1))[:count]
+
+    def call():
+        if feature:
+            return ctx.bufampfeature(x[:, None, :], high_pass_freq=high_pass, sample_rate=float(SR))
+        return ctx.bufampslice(x[:, None, :], on=10.0, off=5.0, high_pass_freq=high_pass, sample_rate=float(SR), capacity=64)
+
+    call()   # warm
+    ctx.synchronize()
+    dev, wall, rounds = [], [], 0
+    ctx.prof_enable(True)
+    for _ in range(reps):
+        ctx.prof_reset()
+        t0 = time.perf_counter()
+        call()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        rounds, ms = ctx.prof_read(2)
+        dev.append(ms)
+    ctx.prof_enable(False)
+    return {"shape": {"buffers": count, "seconds": seconds, "samples": n, "high_pass_freq": high_pass},
+            "client": "BufAmpFeature" if feature else "BufAmpSlice", "device_ms": min(dev), "device_ms_all": dev,
+            "rounds": int(rounds), "wall_ms": min(wall), "serial_steps_per_buffer": n,
+            "plan": ctx.amp_plan(min(high_pass / SR, 0.5))}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--shapes", default="1x10,128x10,8192x2")
+    ap.add_argument("--high-pass", type=float, default=85.0)
+    ap.add_argument("--feature", action="store_true")
+    a = ap.parse_args()
+    ctx = fluhip.Context(0)
+    for s in a.shapes.split(","):
+        count, seconds = s.split("x")
+        print(json.dumps(row(ctx, int(count), float(seconds), a.reps, a.high_pass, a.feature)), flush=True)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -14,6 +14,7 @@ mirrors' tables (include/flucoma_hip/ParamDescriptors.hpp).  tests/test_client.p
     python tools/make_param_descriptor_fixture.py --pitch [/root/reference] > tests/golden/param_descriptors_pitch.json
     python tools/make_param_descriptor_fixture.py --spectral [/root/reference] > tests/golden/param_descriptors_spectral.json
     python tools/make_param_descriptor_fixture.py --loudness [/root/reference] > tests/golden/param_descriptors_loudness.json
+    python tools/make_param_descriptor_fixture.py --amp [/root/reference] > tests/golden/param_descriptors_amp.json
 
 Offline clients the reference composes with makeNRTParams (BufMFCC, BufMelBands: rt/MFCCClient.hpp:171-173,
 rt/MelBandsClient.hpp:151-153) get the wrapper's parameters in front exactly as FluidNRTClientWrapper.hpp:33-39, :747-785
@@ -278,6 +279,18 @@ def main_loudness():
     sys.stdout.write("\n")
 
 
+def main_amp():
+    """--amp: tests/golden/param_descriptors_amp.json, BufAmpSlice (slicing wrapper) and BufAmpFeature (audio wrapper: no
+    padding parameter)"""
+    win = wrapper_inputs()
+    out = {}
+    for name, header in (("BufAmpSlice", "rt/AmpSliceClient.hpp"), ("BufAmpFeature", "rt/AmpFeatureClient.hpp")):
+        bufs = nrt_buffers(header)
+        out[name] = [bufs[0]] + win + bufs[1:] + table(header)
+    json.dump(out, sys.stdout, indent=1)
+    sys.stdout.write("\n")
+
+
 def main():
     win = wrapper_inputs()
     pad = padding_param()
@@ -310,5 +323,7 @@ if __name__ == "__main__":
         main_spectral()
     elif "--loudness" in sys.argv:
         main_loudness()
+    elif "--amp" in sys.argv:
+        main_amp()
     else:
         main()
