@@ -336,9 +336,56 @@ int bufnmfcross_impl(fluhip_ctx* ctx, const float* source, int64_t nSrc, int64_t
   return FLUHIP_OK;
 }
 
+// Diagnostic: one constraint stencil of the H loop -- the launch the clients share -- on the caller's own doubles.
+// H, out [T][K]; which 0: continuity (size = c), 1: temporal sparsity on its zeroing iteration (size = r), 2: polyphony
+// on its zeroing iteration (size = p, energy [K]; the kernel works in place, so it runs on the device copy of H)
+int debug_cross_stencil_impl(fluhip_ctx* ctx, const double* H, int64_t T, int64_t K, int which, int64_t size,
+                             const double* energy, double* out)
+{
+  const char* me = "fluhip_debug_cross_stencil_f64: ";
+  if (!H || !out) return fail(ctx, std::string(me) + "null H or out");
+  if (which < 0 || which > 2) return fail(ctx, std::string(me) + "which must be 0 (continuity), 1 (sparsity) or 2 (polyphony)");
+  if (which == 2 && !energy) return fail(ctx, std::string(me) + "polyphony needs energy");
+  if (T < 1 || K < 1) return fail(ctx, std::string(me) + "T and K must be >= 1");
+  if (T > INT32_MAX || K > INT32_MAX) return fail(ctx, std::string(me) + "too many frames");
+  if (size < 1 || size > (1 << 20)) return fail(ctx, std::string(me) + "size must be from 1 to 1048576");
+  if (which == 2 && size > K) return fail(ctx, std::string(me) + "polyphony must be in [1, K]");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const size_t nb = (size_t) (T * K) * sizeof(double);
+  DevBuf dH, dOut, dE;
+  DEV_ALLOC(ctx, "NMFCross", dH, nb, false);
+  HIPCHK(ctx, hipMemcpyAsync(dH.p, H, nb, hipMemcpyHostToDevice, s));
+  const double* res = dH.as<double>();
+  if (which == 2)
+  {
+    DEV_ALLOC(ctx, "NMFCross", dE, (size_t) K * sizeof(double), false);
+    HIPCHK(ctx, hipMemcpyAsync(dE.p, energy, (size_t) K * sizeof(double), hipMemcpyHostToDevice, s));
+    launch_cross_polyphony(dH.as<double>(), K, (int) T, (int) K, dE.as<double>(), (int) size, s);
+  }
+  else
+  {
+    DEV_ALLOC(ctx, "NMFCross", dOut, nb, false);
+    if (which == 0) launch_cross_continuity(dH.as<double>(), dOut.as<double>(), K, (int) T, (int) K, (int) size, s);
+    else launch_cross_sparsity(dH.as<double>(), dOut.as<double>(), K, (int) T, (int) K, (int) size, s);
+    res = dOut.as<double>();
+  }
+  HIPCHK(ctx, hipGetLastError());
+  int rc = copy_to_host(ctx, out, nb, res, nb, nb, 1, s);
+  if (rc) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  return FLUHIP_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int fluhip_debug_cross_stencil_f64(fluhip_ctx* ctx, const double* H, int64_t T, int64_t K, int which, int64_t size,
+                                   const double* energy, double* out)
+{
+  return guarded(ctx, [&] { return debug_cross_stencil_impl(ctx, H, T, K, which, size, energy, out); });
+}
 
 int fluhip_debug_cross_plan(fluhip_ctx* ctx, int64_t M, int64_t N, int64_t Kd, int64_t* out3)
 {

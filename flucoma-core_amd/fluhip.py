@@ -80,6 +80,7 @@ EXPORTS = [
     "fluhip_amp_envelope_f64", "fluhip_amp_slices_f64", "fluhip_bufampslice_f32", "fluhip_bufampfeature_f32",
     "fluhip_debug_amp_plan",
     "fluhip_debug_features_plan", "fluhip_debug_resynth_f64", "fluhip_debug_corpus_read_layouts_f64",
+    "fluhip_debug_cross_stencil_f64",
 ]
 
 
@@ -142,6 +143,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.fluhip_nmfcross_process_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                               _dp, PROGRESS_FN, _vp]
     L.fluhip_debug_cross_plan.argtypes = [_vp, _i64, _i64, _i64, _ip]
+    L.fluhip_debug_cross_stencil_f64.argtypes = [_vp, _dp, _i64, _i64, ctypes.c_int, _i64, _dp, _dp]
     L.fluhip_debug_jacobi_svd_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _dp, _dp, _dp, _ip]
     L.fluhip_griffinlim_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64]
     L.fluhip_bufnmfcross_f32.argtypes = [_vp, _fp, _i64, _i64, _fp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -589,6 +591,19 @@ class Context:
         out = (_i64 * 3)()
         self._check(self.lib.fluhip_debug_cross_plan(self.h, M, N, Kd, out))
         return bool(out[0]), int(out[1]), int(out[2])
+
+    def cross_stencil(self, H, which, size, energy=None):
+        """fluhip_debug_cross_stencil_f64: one constraint stencil of the H loop on H [T,K] doubles -- which 0 continuity
+        (size c), 1 temporal sparsity on its zeroing iteration (size r), 2 polyphony on its zeroing iteration (size p,
+        energy [K]); returns the new [T,K]"""
+        H = np.ascontiguousarray(H, dtype=np.float64)
+        T, K = H.shape
+        e = None if energy is None else np.ascontiguousarray(energy, dtype=np.float64)
+        assert e is None or e.shape == (K,)
+        out = np.empty((T, K))
+        self._check(self.lib.fluhip_debug_cross_stencil_f64(self.h, _d(H), T, K, which, size, None if e is None else _d(e),
+                                                            _d(out)))
+        return out
 
     def griffinlim(self, spec, n_samples, win, fft, hop, iters=50, seed=42):
         """GriffinLim::process on a complex [T,F] spectrum; returns the new spectrum"""

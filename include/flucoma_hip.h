@@ -41,7 +41,8 @@ extern "C" {
  * fluhip_debug_corpus_read_layouts_f64, fluhip_spectralshape_frames_f64, fluhip_bufspectralshape_f32,
  * fluhip_debug_chroma_filters_f64, fluhip_chroma_frames_f64, fluhip_bufchroma_f32, fluhip_debug_spectral_plan,
  * fluhip_loudness_frames_f64, fluhip_bufloudness_f32, fluhip_debug_loudness_plan, fluhip_amp_envelope_f64,
- * fluhip_amp_slices_f64, fluhip_bufampslice_f32, fluhip_bufampfeature_f32, fluhip_debug_amp_plan. */
+ * fluhip_amp_slices_f64, fluhip_bufampslice_f32, fluhip_bufampfeature_f32, fluhip_debug_amp_plan,
+ * fluhip_debug_cross_stencil_f64. */
 #define FLUHIP_ABI_VERSION 5
 
 /* clients/common/Result.hpp:24  enum class Status { kOk, kWarning, kError, kCancelled } */
@@ -286,6 +287,13 @@ int fluhip_bufnmfcross_f32(fluhip_ctx* ctx, const float* source, int64_t n_src, 
  * M x N output over a contraction of Kd on this context's device: out3 = {1: 128 x 128 workgroup tiles / 0: 64 x 64,
  * contraction splits, split depth}.  What the tests assert the forms they exercise by. */
 int fluhip_debug_cross_plan(fluhip_ctx* ctx, int64_t M, int64_t N, int64_t Kd, int64_t* out3);
+/* Diagnostic: one constraint stencil of the NMFCross H loop, the launch the clients share, on the caller's doubles.
+ * H and out are T x K (frames x source frames, row-major).  which 0: promoteContinuity, size = continuity; 1:
+ * enforceTemporalSparseness on the iteration where its factor is 0, size = time sparsity; 2: restrictPolyphony on that
+ * iteration, size = polyphony <= K, energy[K] required (ignored otherwise).  Null H / out, T or K < 1, size < 1 (or above
+ * 1048576) and polyphony > K are FLUHIP_ERROR with a message.  What tests/test_gpu_nmfcross.py holds bit for bit. */
+int fluhip_debug_cross_stencil_f64(fluhip_ctx* ctx, const double* H, int64_t T, int64_t K, int which, int64_t size,
+                                   const double* energy, double* out);
 
 /* ---- algorithm::Novelty / NoveltyFeature / NoveltySegmentation, clients BufNoveltySlice / BufNoveltyFeature ---- */
 /* Added within version 5 (additive).  FP64 throughout, every buffer of a call in the same launches.

@@ -1,7 +1,28 @@
 """CPU tests of BufNMFCross: the numpy restatement (tests/nmfcross_ref.py) against its loop-by-loop transcription of the
 reference's constraint functions, the integer-division constraint factor, the random draws, the committed goldens, and the
-C ABI's declarations / binding.  No GPU compute."""
+C ABI's declarations / binding.  No GPU compute.
+
+The bars tests/test_gpu_nmfcross.py holds the device to are derived here, each against the long double model and never
+against the device (every figure is recomputed and printed by the tests below):
+
+  CROSS_BAR[iters]  the H loop, entry by entry (nmf_ref.elrel): 8 x the largest elrel of the float64 restatement against
+                    its long double form over every input and (r, p, c) the GPU file runs at that count on a shape small
+                    enough for long double products (nmfcross_ref.bar_cases), made monotone in the count.  8 is NMF_BAR's
+                    factor, for its reason: the quotients of this loop are correctly rounded divisions, so the device
+                    departs from the restatement in summation order alone, the distance the long double form measures.
+                    At 0 iterations the bar is 0: the draw, bit for bit.  A count between two of the table takes the
+                    next one up (cross_bar).  Every quotient times (1 + 2^-40) misses the bar at EVERY input and count.
+  decisions         the long double run's last iteration is at least MARGIN = 1e-8 (relative) from every temporal-sparsity
+                    and polyphony decision at every input: the device, decades closer to it than that, decides the same,
+                    and no entry or frame is exempted on the GPU side.
+  GL_BAR[iters]     Griffin-Lim, frame by frame (gl_frame_err): 64 x the float64 model against the long double one over
+                    the Griffin-Lim cases -- the factor of test_gpu_istft.py and test_gpu_hpss.py: the device's transform
+                    differs from both in the last places.
+  E2E_BAR           the client, of the peak: 64 x the floor + 2^-24 (the float output's rounding), AUDIO_BAR of the HPSS
+                    file; the floor is the float64 against the long double Griffin-Lim and inverse on the same H1.
+"""
 import ctypes
+import functools
 import os
 import re
 
@@ -12,7 +33,60 @@ import nmfcross_ref as R
 import oracle_np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ("fluhip_nmfcross_process_f64", "fluhip_griffinlim_f64", "fluhip_bufnmfcross_f32")
+NEW_SYMBOLS = ("fluhip_nmfcross_process_f64", "fluhip_griffinlim_f64", "fluhip_bufnmfcross_f32", "fluhip_debug_cross_stencil_f64")
+
+# How a bar follows from the figures (as tests/test_nmf_ref.py): the factor times the worst figure of that count, made monotone
+# in the count, plus 3 % for another BLAS or FFT build's roundings, rounded up to two digits.  The tests recompute every figure
+# on the host they run on and hold the constants to "covers, and no looser than the rule".
+HEADROOM = 1.03
+# Measured with one BLAS thread, float64 against long double (elrel), the worst of 60 .. 66 inputs x constraint sets per count:
+#   1  4.374e-15 at 300x200x513 (3, 300, 5)    2  5.492e-15 at 259x173x513 (3, 259, 5)    3  4.973e-15 at 300x200x513 (7, 11, 7)
+#  10  7.158e-15 at 37x61x129 (3, 37, 5)      50  3.782e-14 at 259x173x513 (3, 259, 5); 3x5x9 and smaller about 3e-16 throughout;
+#   4  2.266e-15 (the strided case) and 5  6.661e-15 (150x90x257) under the bar of 10.
+# Every quotient times (1 + 2^-40) costs 9.09e-13 .. 9.47e-13 at every input and count.  The smallest decision margins:
+# temporal sparsity 2.1e-7 (50 iterations), polyphony 3.7e-5 (1 iteration).
+CROSS_BAR = {0: 0.0, 1: 3.7e-14, 2: 4.6e-14, 3: 4.6e-14, 10: 5.9e-14, 50: 3.2e-13}
+MARGIN = 1e-8
+# float64 against long double Griffin-Lim, the worst frame of the worst case (3000, 256, 512, 64 at every count):
+#   0  2.965e-16    1  2.958e-15    2  7.037e-15    3  4.526e-14    50  1.104e-12
+GL_BAR = {0: 2.0e-14, 1: 2.0e-13, 2: 4.7e-13, 3: 3.0e-12, 50: 7.3e-11}
+E2E_FLOOR = 1.3e-12    # measured 1.176e-12, one BLAS thread (20000 -> 9000 samples, window 1000 of fft 1024; the others 5.2e-14 .. 7.8e-13)
+E2E_BAR = 64 * E2E_FLOOR + 2.0 ** -24
+
+
+def cross_bar(iters):
+    """the bar of an iteration count: its own, or that of the next count up in the table (a monotone table)"""
+    return CROSS_BAR[min(i for i in CROSS_BAR if i >= iters)]
+
+
+def round_up_two_digits(x):
+    if x == 0:
+        return 0.0
+    e = int(np.floor(np.log10(x))) - 1
+    return float(f"{np.ceil(x / 10.0 ** e * (1 - 1e-12)) * 10.0 ** e:.1e}")
+
+
+@functools.lru_cache(maxsize=None)
+def measured_cross(iters):
+    """{name: (float64 against long double, every quotient times 1 + 2^-40 against long double, the two decision margins)}
+    of every bar case of this count: computed once, with one BLAS thread (the float64 products' summation order follows the
+    thread count)"""
+    import threadpoolctl
+    assert np.finfo(np.longdouble).eps < 2e-19
+    out = {}
+    with threadpoolctl.threadpool_limits(limits=1):
+        for name, X, W0, rpc, hseed in R.bar_cases(iters):
+            ld, margins = R.nmfcross_ld(X, W0, *rpc, iters, hseed)
+            f64 = R.elrel(R.nmfcross(X, W0, *rpc, iters, hseed), ld)
+            far = R.elrel(R.nmfcross(X, W0, *rpc, iters, hseed, perturb=2.0 ** -40), ld)
+            out[name] = (f64, far, margins)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def measured_gl(iters):
+    return {c: R.gl_frame_err(R.griffinlim(R.gl_input(*c), c[0], iters, *c[1:], R.GL_SEED),
+                              R.griffinlim_ld(R.gl_input(*c), c[0], iters, *c[1:], R.GL_SEED)) for c in R.GL_CASES}
 
 
 def _random_h(K, T, seed, zeros=0.3):
@@ -75,6 +149,134 @@ def test_literal_and_vectorised_pipelines_agree():
         np.testing.assert_allclose(a, b, rtol=1e-13, atol=0)
 
 
+# ---- the bars ----------------------------------------------------------------------------------------------------------------
+def test_cross_bar_covers_float64_against_long_double():
+    assert set(CROSS_BAR) == set(R.ITERS) and CROSS_BAR[0] == 0.0
+    envelope = 0.0
+    for iters in R.ITERS:
+        worst, where = 0.0, None
+        for name, (f64, _, _) in measured_cross(iters).items():
+            print(f"{name} x {iters}: float64 against long double {f64:.3e}")
+            if f64 >= worst:
+                worst, where = f64, name
+        envelope = max(envelope, 8 * worst)
+        want = round_up_two_digits(envelope * HEADROOM)
+        print(f"x {iters}: worst {worst:.3e} at {where}, x 8 = {8 * worst:.3e}, monotone {envelope:.3e}, + 3 % rounded up "
+              f"{want:.1e} (bar {CROSS_BAR[iters]:.1e})")
+        assert 8 * worst <= CROSS_BAR[iters] <= 1.1 * want, (iters, worst, want)     # covers, and is not looser than the rule
+    for iters in (4, 5):                          # counts between two of the table take the next one up
+        for name, (f64, _, _) in measured_cross(iters).items():
+            print(f"{name} x {iters}: float64 against long double {f64:.3e} (bar {cross_bar(iters):.1e})")
+            assert 8 * f64 <= cross_bar(iters)
+    assert cross_bar(4) == cross_bar(5) == CROSS_BAR[10] and cross_bar(0) == 0.0
+
+
+def test_no_iteration_is_the_draw_bit_for_bit():
+    for name, X, W0, rpc, hseed in R.bar_cases(0):
+        H = R.nmfcross(X, W0, *rpc, 0, hseed)
+        assert np.array_equal(H, R.initial_h(W0.shape[0], X.shape[0], hseed).T), name
+        assert np.array_equal(H, R.nmfcross(X, W0, *rpc, 0, hseed, dtype=np.longdouble).astype(np.float64))
+
+
+@pytest.mark.parametrize("iters", [i for i in R.ITERS if i] + [4, 5])
+def test_cross_bar_has_teeth_quotients_off_by_2_to_the_minus_40_miss_it(iters):
+    for name, (_, far, _) in measured_cross(iters).items():
+        print(f"{name} x {iters}: quotients times 1 + 2^-40 cost {far:.3e} (bar {cross_bar(iters):.1e})")
+        assert far > cross_bar(iters), (name, far)
+
+
+@pytest.mark.parametrize("iters", [i for i in R.ITERS if i] + [4, 5])
+def test_every_decision_of_the_last_iteration_has_a_margin(iters):
+    lo = [np.inf, np.inf]
+    for name, (_, _, m) in measured_cross(iters).items():
+        print(f"{name} x {iters}: sparsity margin {m[0]:.3e}, polyphony margin {m[1]:.3e}")
+        assert min(m) >= MARGIN, (name, m)
+        lo = [min(a, b) for a, b in zip(lo, m)]
+    print(f"x {iters}: smallest margins {lo[0]:.3e} (sparsity) {lo[1]:.3e} (polyphony), required {MARGIN:.0e}")
+
+
+def test_decision_margins_sees_a_near_tie():
+    X, W0 = R.loop_inputs(3, 5, 9)
+    assert R.decision_margins(X, W0, 3, 2, 3, 0, 1) == (np.inf, np.inf)
+    assert R.decision_margins(X, W0, 1, 3, 3, 2, 1) == (np.inf, np.inf)      # r == 1 and p == K decide nothing
+    W2 = np.vstack([W0[:2], W0[1:2] * (1 + 1e-12)])                          # two source frames 1e-12 apart
+    seed = next(s for s in range(200) if abs(np.subtract(*R.initial_h(3, 5, s)[1:3, 0])) < 0.02)
+    a = R.decision_margins(X, W2, 1, 1, 1, 1, seed)
+    assert a[0] == np.inf and 0 < a[1] < 0.05, a
+
+
+def test_perturb_scales_every_quotient():
+    X, W0 = R.loop_inputs(3, 5, 9)
+    a, b = R.nmfcross(X, W0, 3, 2, 3, 1, 1), R.nmfcross(X, W0, 3, 2, 3, 1, 1, perturb=2.0 ** -20)
+    live = a > 0
+    np.testing.assert_allclose(b[live] / a[live], 1 + 2.0 ** -20, rtol=1e-12)
+    assert np.array_equal(a, R.nmfcross(X, W0, 3, 2, 3, 1, 1, perturb=0.0))
+
+
+def test_silence_gives_rows_of_exact_zeros():
+    X, W0 = R.silence_inputs()
+    K, T, _ = R.SILENCE
+    for iters in R.SILENCE_ITERS:
+        H = R.nmfcross(X, W0, *R.SILENCE_RPC, iters, R.H_SEED, dtype=np.longdouble)
+        assert np.isfinite(H.astype(np.float64)).all()
+        assert not H[[0, 7, 8, 9, T - 1]].any() and H.any()
+
+
+def test_gl_bar_covers_float64_against_long_double():
+    assert set(GL_BAR) == set(R.GL_ITERS)
+    envelope = 0.0
+    for iters in R.GL_ITERS:
+        for c, e in measured_gl(iters).items():
+            print(f"griffinlim {c} x {iters}: float64 against long double, worst frame {e:.3e}")
+        worst = max(measured_gl(iters).values())
+        envelope = max(envelope, 64 * worst)
+        want = round_up_two_digits(envelope * HEADROOM)
+        print(f"griffinlim x {iters}: worst {worst:.3e}, x 64 = {64 * worst:.3e}, monotone {envelope:.3e}, + 3 % rounded up {want:.1e} "
+              f"(bar {GL_BAR[iters]:.1e})")
+        assert 64 * worst <= GL_BAR[iters] <= 1.1 * want, (iters, worst, want)
+    assert GL_BAR[50] < 1e-9           # tighter than the assertion it replaces
+
+
+def test_long_double_inverse_and_griffinlim_restate_the_float64_ones():
+    n, win, fft, hop = R.GL_CASES[2]
+    spec = R.gl_input(n, win, fft, hop)
+    a, b = R.istft(spec, n, win, fft, hop), R.istft_ld(spec, n, win, fft, hop)
+    assert np.abs(a - b).max() <= 1e-14 * np.abs(b).max()
+    x = oracle_np.synth_audio(n, 5)
+    back = R.istft_ld(oracle_np.stft(x, win, fft, hop)[0], n, win, fft, hop)
+    assert np.abs(back - x).max() <= 1e-13
+    z = np.zeros_like(spec)
+    z[3:] = spec[3:]
+    g = R.griffinlim_ld(z, n, 0, win, fft, hop, 1)
+    assert not g[:3].any() and R.gl_frame_err(R.griffinlim(z, n, 0, win, fft, hop, 1), g) < 1e-15
+    with pytest.raises(AssertionError):
+        R.gl_frame_err(np.ones((2, 3)), np.array([[1.0, 1, 1], [0, 0, 0]]))       # a silent frame must be silent
+
+
+def test_e2e_bar_from_the_floor_between_float64_and_long_double():
+    import threadpoolctl
+    worst = 0.0
+    for n_src, n_tgt, win, fft, hop in R.CLIENT:
+        src, tgt = R.client_audio(n_src, n_tgt)
+        r, p, c = R.client_rpc(n_tgt, hop)
+        with threadpoolctl.threadpool_limits(limits=1):     # (H1's last places follow the BLAS thread count, and 50 iterations amplify them)
+            e = R.e2e_floor(src, tgt, win, fft, hop, r, p, c, 50, 42)
+        print(f"client {(n_src, n_tgt, win, fft, hop)}: float64 against long double Griffin-Lim + inverse {e:.3e} of the peak")
+        worst = max(worst, e)
+    print(f"floor {worst:.3e} (constant {E2E_FLOOR:.1e}); E2E_BAR = 64 x floor + 2^-24 = {E2E_BAR:.3e}")
+    assert worst <= E2E_FLOOR <= 1.1 * round_up_two_digits(worst * HEADROOM)
+    assert E2E_BAR < 1e-6 / 15
+
+
+def test_the_forced_splits_reach_a_short_last_chunk():
+    """the contractions of the EDGE shapes under a forced three-way split: 65 = 32 + 32 + 1, 127 = 48 + 48 + 31, 33 = 16 + 16 + 1"""
+    depths = sorted({d for K, _, F in R.EDGE for d in (K, F)})
+    assert depths == [1, 15, 16, 17, 33, 65, 127, 129]
+    got = {Kd: R.forced_splits(Kd, 3) for Kd in depths}
+    assert got == {1: (1, 16), 15: (1, 16), 16: (1, 16), 17: (2, 16), 33: (3, 16), 65: (3, 32), 127: (3, 48), 129: (3, 48)}
+    assert all(R.forced_splits(Kd, 1) == (1, -(-Kd // 16) * 16) for Kd in depths)
+
+
 def test_initial_h_is_the_column_major_fill():
     u = oracle_np.rng_uniform01(42, 12)
     H = R.initial_h(3, 4, 42)            # K x T column-major: entry (k, t) is draw t K + k
@@ -129,7 +331,7 @@ def test_binding_lists_the_nmfcross_entries():
     import fluhip
     for name in NEW_SYMBOLS:
         assert name in fluhip.EXPORTS
-    for meth in ("nmfcross_process", "griffinlim", "bufnmfcross"):
+    for meth in ("nmfcross_process", "griffinlim", "bufnmfcross", "cross_stencil"):
         assert callable(getattr(fluhip.Context, meth))
 
 
