@@ -135,6 +135,91 @@ int fluhip_debug_resynth_f64(fluhip_ctx* ctx, const double* spec, int64_t T, int
   return guarded(ctx, [&] { return debug_resynth_impl(ctx, spec, T, win, fft, hop, n, trim, W, H, K, out); });
 }
 
+} // extern "C" (a template)
+
+// Diagnostic: T frames from an ARBITRARY first sample through the clients' own launch (stft_setup, StftSetup::args,
+// StftSetup::launch: the kernel form is the dispatcher's choice) -- frames that start before sample -fft or at or behind
+// sample n included, which STFT::process' framing never produces and the control clients' latency does.  Every buffer comes
+// with `guard` samples of the caller's choosing in front of it and behind it, [B][guard + n + guard]; the kernels get the
+// pointer to the n samples, n and the padded stride.  A sample taken from outside [0, n) instead of zero then shows in the
+// result as whatever the caller put there, and the guards are required to reach as far as the furthest frame plus one
+// transform, so that whatever a kernel loads for a frame of this call lies inside the call's own allocation.
+template <typename S>
+static int debug_stft_frames_impl(fluhip_ctx* ctx, const char* me, const S* padded, int64_t B, int64_t n, int64_t guard,
+                                  int64_t win, int64_t fft, int64_t hop, int64_t frame0, int64_t T, double* spec, double* mag)
+{
+  if (!padded || (!spec && !mag)) return fail(ctx, std::string(me) + "null input, or neither spec nor mag");
+  if (int rc = check_fft_settings(ctx, win, fft, hop)) return rc;
+  if (B < 1 || B > 64) return fail(ctx, std::string(me) + "B must be from 1 to 64");
+  if (T < 1 || T > 65536) return fail(ctx, std::string(me) + "T must be from 1 to 65536");
+  if (n < 0 || n > 100000000LL) return fail(ctx, std::string(me) + "n must be from 0 to 100000000");
+  if (hop > 1000000 || frame0 < -1000000000LL || frame0 > 1000000000LL)
+    return fail(ctx, std::string(me) + "hop at most 1000000, frame0 within +-1000000000");
+  const int64_t first = frame0, end = frame0 + (T - 1) * hop + fft; // the samples any frame spans, padded to the transform
+  const int64_t need = std::max<int64_t>(std::max<int64_t>(-first, end - n), 0) + fft;
+  if (guard < need || guard > 100000000LL)
+    return fail(ctx, std::string(me) + "the guards must reach as far as the furthest frame lies outside the buffer, plus fft: " +
+                         std::to_string(need) + " samples");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  StftSetup st;
+  int rc = stft_setup(ctx, win, fft, hop, &st);
+  if (rc) return rc;
+  const int64_t F = st.F, Fp = round_up(F, 32), stride = n + 2 * guard;
+  DevBuf in, dspec, dmag;
+  DEV_ALLOC(ctx, "input", in, (size_t) B * stride * sizeof(S), false);
+  HIPCHK(ctx, hipMemcpyAsync(in.p, padded, (size_t) B * stride * sizeof(S), hipMemcpyHostToDevice, s));
+  const S* samples = in.as<S>() + guard;
+  StftArgs sa;
+  if constexpr (sizeof(S) == sizeof(float))
+    sa = st.args(samples, nullptr, n, stride, B, T, frame0);
+  else
+    sa = st.args(nullptr, samples, n, stride, B, T, frame0);
+  if (spec)
+  {
+    DEV_ALLOC(ctx, "spectrum", dspec, (size_t) B * T * F * 2 * sizeof(double), true);
+    sa.spec = dspec.as<double>(); sa.specStride = T * F * 2;
+  }
+  if (mag)
+  {
+    DEV_ALLOC(ctx, "magnitude", dmag, (size_t) B * T * Fp * sizeof(double), true);
+    sa.mag = dmag.as<double>(); sa.magStride = T * Fp; sa.ldMag = Fp;
+  }
+  if ((rc = st.launch(ctx, sa))) return rc;
+  // with the spectrum the magnitudes are hypot of it, as fluhip_stft_* return them (stft_common: an exact 0 for silence);
+  // without it they are the kernels' own, where the block form's sqrt from DBL_MIN leaves 2^-511 for an exactly silent bin
+  if (spec && mag) launch_mag_hypot(dspec.as<double>(), (int) (B * T), (int) F, dmag.as<double>(), Fp, s);
+  HIPCHK(ctx, hipGetLastError());
+  if (spec)
+  {
+    const size_t nb = (size_t) B * T * F * 2 * sizeof(double);
+    if ((rc = copy_to_host(ctx, spec, nb, dspec.p, nb, nb, 1, s))) return rc;
+  }
+  if (mag && (rc = copy_to_host(ctx, mag, (size_t) F * sizeof(double), dmag.p, (size_t) Fp * sizeof(double),
+                                (size_t) F * sizeof(double), (size_t) (B * T), s)))
+    return rc;
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  return FLUHIP_OK;
+}
+
+extern "C" {
+
+int fluhip_debug_stft_frames_f32(fluhip_ctx* ctx, const float* padded, int64_t B, int64_t n, int64_t guard, int64_t win,
+                                 int64_t fft, int64_t hop, int64_t frame0, int64_t T, double* spec, double* mag)
+{
+  return guarded(ctx, [&] {
+    return debug_stft_frames_impl(ctx, "fluhip_debug_stft_frames_f32: ", padded, B, n, guard, win, fft, hop, frame0, T, spec, mag);
+  });
+}
+
+int fluhip_debug_stft_frames_f64(fluhip_ctx* ctx, const double* padded, int64_t B, int64_t n, int64_t guard, int64_t win,
+                                 int64_t fft, int64_t hop, int64_t frame0, int64_t T, double* spec, double* mag)
+{
+  return guarded(ctx, [&] {
+    return debug_stft_frames_impl(ctx, "fluhip_debug_stft_frames_f64: ", padded, B, n, guard, win, fft, hop, frame0, T, spec, mag);
+  });
+}
+
 // ---- two-stride views at the algorithm boundary (data/FluidTensor_Support.hpp:260-420, util/FluidEigenMappings.hpp:35-225)
 } // extern "C" (the helpers below are C++)
 namespace {

@@ -6,9 +6,11 @@
 // kernels_ampgate.hip (fluhip_ampgate.h).  No event, no stream is taken.  The device buffers of a call are its own (GateBuf:
 // hipMalloc, hipFree when the call ends) and do NOT go through the caching block pool: a gate call asks for blocks of many sizes
 // (a plane and a record row per signal of n + latency samples, byte planes of n), and what it would leave in the cache is what a
-// later call of another entry point is handed.  While the STFT gather still reads behind a buffer for a frame that lies wholly
-// outside it that decides whether such a call faults; a gate call leaves the cache exactly as it found it.  The
-// price is one hipMalloc / hipFree per buffer and call, a millisecond or two of a call that runs two serial passes.
+// later call of another entry point is handed.  That mattered while the STFT gather loaded one sample outside its buffer for a
+// frame that lay wholly outside it (closed: the gather's loads stay inside [0, n), frame_window.h) -- what the
+// cache held then decided whether such a call faulted; a gate call leaves the cache exactly as it found it.  The form is kept
+// as it is (undoing it changes allocation and timing and is a change of its own).  The price is one hipMalloc / hipFree per
+// buffer and call, a millisecond or two of a call that runs two serial passes.
 #include "api_internal.h"
 #include "fluhip_amp.h"
 #include "fluhip_ampgate.h"

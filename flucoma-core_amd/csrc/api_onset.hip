@@ -32,8 +32,9 @@ int check_slice_params(fluhip_ctx* ctx, double threshold, int64_t minSlice)
 
 // the frames of `nb` equal-length signals on the device: frame i's window starts at sample base + i hop, the second
 // transform of a frame-delta form frameDelta samples on.  The callers lay the signals out with their zeros around them
-// (onset_padded_length) so that EVERY frame lies inside its row: the STFT kernels' clamped gather reads one sample of the
-// row even for a frame that lies wholly outside it, which is then outside the allocation.
+// (onset_padded_length) so that EVERY frame lies inside its row.  (The layout dates from when the STFT kernels' clamped
+// gather loaded one sample outside the row for a frame that lay wholly outside it; the gather's loads now stay inside
+// [0, n) for any frame, frame_window.h, and the zeros are kept because the kernels' arithmetic and timing rest on them.)
 struct OnsetRun
 {
   fluhip_ctx* ctx;

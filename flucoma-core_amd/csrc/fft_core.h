@@ -20,6 +20,7 @@
 #pragma once
 
 #include "fluhip_kernels.h"
+#include "frame_window.h"
 
 namespace fluhip {
 
@@ -758,14 +759,21 @@ __device__ __forceinline__ void gather_points(const StftBArgs& a, int b, int t, 
   const int64_t s0 = (int64_t) t * a.hop - a.win / 2 + a.frameOffset;
   // ---- gather + window: point m = x[2m] + i x[2m+1], m = lane + 64 bb + r N/R1 --------------------
   // sample positions are 32-bit offsets from the frame's first sample (a wave-uniform 64-bit base); only frames
-  // that stick out of the buffer (or an odd base) take the clamped path
-  const int lo = s0 < 0 ? (int) (-s0 < 2 * N ? -s0 : 2 * N) : 0;                 // first valid offset
-  const int64_t room = nSamples - s0;
-  const int hi = room < 2 * N ? (int) (room > 0 ? room : 0) : 2 * N;             // one past the last valid offset
+  // that stick out of the buffer (or an odd base) take the clamped path.  Which offsets are samples of the buffer and
+  // where the load of every other one goes is frame_window.h's rule: always a sample of [0, n), counted from the
+  // buffer's own first sample for a frame that lies wholly outside it (a wave-uniform choice: s0 and n decide it)
+  const FrameWindow fw = frame_window(s0, 2 * N, nSamples);
+  if (!fw.loads)
+  {
+    // an empty buffer: every sample reads as zero and nothing is loaded
+#pragma unroll
+    for (int i = 0; i < N / 64; i++) pts[i] = cx{0.0, 0.0};
+    return;
+  }
   if (a.audio)
   {
-    const float* fp = a.audio + (int64_t) b * a.audioStride + s0;
-    const bool fast = lo == 0 && hi == 2 * N && ((reinterpret_cast<uintptr_t>(fp) & 7) == 0);
+    const float* fp = a.audio + (int64_t) b * a.audioStride + fw.origin;
+    const bool fast = fw.lo == 0 && fw.hi == 2 * N && ((reinterpret_cast<uintptr_t>(fp) & 7) == 0);
     if (fast)
     {
       const float2* lp = reinterpret_cast<const float2*>(fp) + lane;
@@ -791,8 +799,8 @@ __device__ __forceinline__ void gather_points(const StftBArgs& a, int b, int t, 
         {
           const int mo = 64 * bb + r * (N / R1);
           const int i0 = 2 * (ln + mo), i1 = i0 + 1;
-          const bool ok0 = i0 >= lo && i0 < hi, ok1 = i1 >= lo && i1 < hi;
-          const float v0 = fp[ok0 ? i0 : lo], v1 = fp[ok1 ? i1 : lo];   // lo is a valid offset whenever hi > lo
+          const bool ok0 = frame_ok(fw, i0), ok1 = frame_ok(fw, i1);
+          const float v0 = fp[frame_load_offset(fw, i0)], v1 = fp[frame_load_offset(fw, i1)];
           const d2 w = wsrc[lane + mo];
           pts[bb * R1 + r] = cx{(ok0 ? (double) v0 : 0.0) * w[0], (ok1 ? (double) v1 : 0.0) * w[1]};
         }
@@ -800,7 +808,7 @@ __device__ __forceinline__ void gather_points(const StftBArgs& a, int b, int t, 
   }
   else
   {
-    const double* dp = a.audio64 + (int64_t) b * a.audioStride + s0;
+    const double* dp = a.audio64 + (int64_t) b * a.audioStride + fw.origin;
     int ln = lane;
     asm volatile("" : "+v"(ln));
 #pragma unroll
@@ -810,8 +818,8 @@ __device__ __forceinline__ void gather_points(const StftBArgs& a, int b, int t, 
       {
         const int mo = 64 * bb + r * (N / R1);
         const int i0 = 2 * (ln + mo), i1 = i0 + 1;
-        const bool ok0 = i0 >= lo && i0 < hi, ok1 = i1 >= lo && i1 < hi;
-        const double v0 = dp[ok0 ? i0 : lo], v1 = dp[ok1 ? i1 : lo];
+        const bool ok0 = frame_ok(fw, i0), ok1 = frame_ok(fw, i1);
+        const double v0 = dp[frame_load_offset(fw, i0)], v1 = dp[frame_load_offset(fw, i1)];
         const d2 w = wsrc[lane + mo];
         pts[bb * R1 + r] = cx{(ok0 ? v0 : 0.0) * w[0], (ok1 ? v1 : 0.0) * w[1]};
       }

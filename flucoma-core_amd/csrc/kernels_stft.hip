@@ -18,6 +18,7 @@
 //      fused with |X| and the coalesced store of the magnitude row (and optionally X itself).
 // HBM traffic per frame: hop*4 B of unique samples in (overlapping reads hit L2), F*8 B out.
 #include "fluhip_kernels.h"
+#include "frame_window.h"
 
 #include <cstdlib>
 
@@ -352,7 +353,7 @@ __global__ __launch_bounds__(64 * MAXW) void stft_wave_kernel(StftKArgs a)
     const int b = (int) (frame / a.T), t = (int) (frame % a.T);
     const int64_t s0 = (int64_t) t * a.hop - halfWin + a.frameOffset;
     const float* src = a.audio + (int64_t) b * a.audioStride;
-    const int64_t last = a.n - 1;
+    const bool loads = a.n > 0;                 // (an empty buffer: nothing is loaded, frame_window.h)
 #pragma unroll
     for (int bb = 0; bb < NB1; bb++)
 #pragma unroll
@@ -360,16 +361,16 @@ __global__ __launch_bounds__(64 * MAXW) void stft_wave_kernel(StftKArgs a)
       {
         const int m = lane + 64 * bb + r * (N / R1);
         const int64_t p0 = s0 + 2 * m, p1 = p0 + 1;
-        const float v0 = src[p0 < 0 ? 0 : (p0 > last ? last : p0)];
-        const float v1 = src[p1 < 0 ? 0 : (p1 > last ? last : p1)];
-        raw[bb * R1 + r] = make_float2((p0 >= 0 && p0 <= last) ? v0 : 0.f, (p1 >= 0 && p1 <= last) ? v1 : 0.f);
+        const float v0 = loads ? src[frame_clamped_sample(p0, a.n)] : 0.f;
+        const float v1 = loads ? src[frame_clamped_sample(p1, a.n)] : 0.f;
+        raw[bb * R1 + r] = make_float2(frame_sample_ok(p0, a.n) ? v0 : 0.f, frame_sample_ok(p1, a.n) ? v1 : 0.f);
       }
   };
   auto gather64 = [&](int64_t frame, d2 (&pts)[PPL]) {
     const int b = (int) (frame / a.T), t = (int) (frame % a.T);
     const int64_t s0 = (int64_t) t * a.hop - halfWin + a.frameOffset;
     const double* src = a.audio64 + (int64_t) b * a.audioStride;
-    const int64_t last = a.n - 1;
+    const bool loads = a.n > 0;
 #pragma unroll
     for (int bb = 0; bb < NB1; bb++)
 #pragma unroll
@@ -377,10 +378,10 @@ __global__ __launch_bounds__(64 * MAXW) void stft_wave_kernel(StftKArgs a)
       {
         const int m = lane + 64 * bb + r * (N / R1);
         const int64_t p0 = s0 + 2 * m, p1 = p0 + 1;
-        const double v0 = src[p0 < 0 ? 0 : (p0 > last ? last : p0)];
-        const double v1 = src[p1 < 0 ? 0 : (p1 > last ? last : p1)];
+        const double v0 = loads ? src[frame_clamped_sample(p0, a.n)] : 0.0;
+        const double v1 = loads ? src[frame_clamped_sample(p1, a.n)] : 0.0;
         const d2 w = wlds[m];
-        pts[bb * R1 + r] = d2{((p0 >= 0 && p0 <= last) ? v0 : 0.0) * w[0], ((p1 >= 0 && p1 <= last) ? v1 : 0.0) * w[1]};
+        pts[bb * R1 + r] = d2{(frame_sample_ok(p0, a.n) ? v0 : 0.0) * w[0], (frame_sample_ok(p1, a.n) ? v1 : 0.0) * w[1]};
       }
   };
 
@@ -417,7 +418,7 @@ __global__ __launch_bounds__(64 * MAXW) void stft_wave_kernel(StftKArgs a)
       }
       else
       {
-        const int64_t last = a.n - 1;
+        const bool loads = a.n > 0;
 #pragma unroll
         for (int bb = 0; bb < NB1; bb++)
 #pragma unroll
@@ -425,10 +426,10 @@ __global__ __launch_bounds__(64 * MAXW) void stft_wave_kernel(StftKArgs a)
           {
             const int m = lane + 64 * bb + r * (N / R1);
             const int64_t p0 = s0 + 2 * m, p1 = p0 + 1;
-            const float v0 = src[p0 < 0 ? 0 : (p0 > last ? last : p0)];
-            const float v1 = src[p1 < 0 ? 0 : (p1 > last ? last : p1)];
-            const double x0 = (p0 >= 0 && p0 <= last) ? (double) v0 : 0.0;
-            const double x1 = (p1 >= 0 && p1 <= last) ? (double) v1 : 0.0;
+            const float v0 = loads ? src[frame_clamped_sample(p0, a.n)] : 0.f;
+            const float v1 = loads ? src[frame_clamped_sample(p1, a.n)] : 0.f;
+            const double x0 = frame_sample_ok(p0, a.n) ? (double) v0 : 0.0;
+            const double x1 = frame_sample_ok(p1, a.n) ? (double) v1 : 0.0;
             const d2 w = wlds[m]; // zero past the window length
             pts[bb * R1 + r] = d2{x0 * w[0], x1 * w[1]};
           }

@@ -81,7 +81,7 @@ EXPORTS = [
     "fluhip_debug_amp_plan",
     "fluhip_amp_gate_f64", "fluhip_bufampgate_f32", "fluhip_debug_ampgate_plan",
     "fluhip_debug_features_plan", "fluhip_debug_resynth_f64", "fluhip_debug_corpus_read_layouts_f64",
-    "fluhip_debug_cross_stencil_f64",
+    "fluhip_debug_cross_stencil_f64", "fluhip_debug_stft_frames_f32", "fluhip_debug_stft_frames_f64",
 ]
 
 
@@ -118,6 +118,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.fluhip_stft_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, _dp, _dp, _ip]
     L.fluhip_stft_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, _dp, _dp, _ip]
     L.fluhip_debug_resynth_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _dp, _dp, _i64, _dp]
+    L.fluhip_debug_stft_frames_f32.argtypes = [_vp, _fp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _dp, _dp]
+    L.fluhip_debug_stft_frames_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _dp, _dp]
     L.fluhip_nmf_process_f64.argtypes = [_vp, _dp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int,
                                          ctypes.c_int, _i64, _dp, _dp, _dp, _dp, _dp, PROGRESS_FN, _vp]
     _mv = ctypes.POINTER(MatrixView)
@@ -369,6 +371,22 @@ class Context:
         assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == shape
         self._check(self.lib.fluhip_debug_resynth_f64(self.h, _d(spec), T, win, fft, hop, n, trim, _d(Wc), _d(Hc), K, _d(out)))
         return out
+
+    def debug_stft_frames(self, padded, n, guard, win, fft, hop, frame0, T, want_spec=True, want_mag=True):
+        """fluhip_debug_stft_frames_f32 / _f64: T frames of every row of `padded` [B, guard + n + guard] (float32 or float64;
+        the n samples of a buffer between guards of the caller's choosing), frame t at samples [frame0 + t hop, + win) of its
+        buffer, zero outside [0, n).  Returns (spec complex [B, T, F] or None, mag [B, T, F] or None)."""
+        padded = np.ascontiguousarray(padded)
+        assert padded.ndim == 2 and padded.shape[1] == n + 2 * guard and padded.dtype in (np.float32, np.float64)
+        B, F = padded.shape[0], fft // 2 + 1
+        spec = np.empty((B, T, F, 2)) if want_spec else None
+        mag = np.empty((B, T, F)) if want_mag else None
+        if padded.dtype == np.float32:
+            rc = self.lib.fluhip_debug_stft_frames_f32(self.h, _f(padded), B, n, guard, win, fft, hop, frame0, T, _d(spec), _d(mag))
+        else:
+            rc = self.lib.fluhip_debug_stft_frames_f64(self.h, _d(padded), B, n, guard, win, fft, hop, frame0, T, _d(spec), _d(mag))
+        self._check(rc)
+        return (spec[..., 0] + 1j * spec[..., 1] if want_spec else None), mag
 
     # ---- algorithm::NMF -----------------------------------------------------------------
     def nmf_process(self, X, K, iters, updateW=True, updateH=True, seed=42, W0=None, H0=None,

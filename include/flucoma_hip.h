@@ -42,7 +42,8 @@ extern "C" {
  * fluhip_debug_chroma_filters_f64, fluhip_chroma_frames_f64, fluhip_bufchroma_f32, fluhip_debug_spectral_plan,
  * fluhip_loudness_frames_f64, fluhip_bufloudness_f32, fluhip_debug_loudness_plan, fluhip_amp_envelope_f64,
  * fluhip_amp_slices_f64, fluhip_bufampslice_f32, fluhip_bufampfeature_f32, fluhip_debug_amp_plan,
- * fluhip_debug_cross_stencil_f64, fluhip_amp_gate_f64, fluhip_bufampgate_f32, fluhip_debug_ampgate_plan. */
+ * fluhip_debug_cross_stencil_f64, fluhip_amp_gate_f64, fluhip_bufampgate_f32, fluhip_debug_ampgate_plan,
+ * fluhip_debug_stft_frames_f32, fluhip_debug_stft_frames_f64. */
 #define FLUHIP_ABI_VERSION 5
 
 /* clients/common/Result.hpp:24  enum class Status { kOk, kWarning, kError, kCancelled } */
@@ -136,6 +137,20 @@ int fluhip_stft_f32(fluhip_ctx* ctx, const float* audio, int64_t n, int64_t stri
  * Bad arguments: FLUHIP_ERROR with a message that names them, out untouched. */
 int fluhip_debug_resynth_f64(fluhip_ctx* ctx, const double* spec, int64_t T, int64_t win, int64_t fft, int64_t hop, int64_t n,
                              int64_t trim, const double* W, const double* H, int64_t K, double* out);
+
+/* Diagnostic: T frames of each of B buffers from an arbitrary first sample -- frame t of a buffer is its samples
+ * [frame0 + t hop, + win), zero outside [0, n); frame0 may lie any distance before the buffer and the frames may run any
+ * distance behind it -- through the same tables, launch and choice of kernel form as every client's forward transform.
+ * padded: B x (guard + n + guard) samples, every buffer's n samples between `guard` samples of the caller's choosing, which
+ * no result may depend on; guard >= the furthest any frame lies outside its buffer + fft (checked), so that nothing a kernel
+ * loads for these frames leaves the call's own allocation.  spec: B x T x F interleaved (re,im) doubles, mag: B x T x F
+ * doubles, either may be NULL.  With spec the magnitudes are hypot of it, as fluhip_stft_* return them (exactly 0 for a silent
+ * bin); without it they are the kernels' own, as the corpus and the control clients consume them (the block form leaves
+ * sqrt(DBL_MIN) = 2^-511 for an exactly silent bin).  Bad arguments: FLUHIP_ERROR with a message that names them. */
+int fluhip_debug_stft_frames_f32(fluhip_ctx* ctx, const float* padded, int64_t B, int64_t n, int64_t guard, int64_t win,
+                                 int64_t fft, int64_t hop, int64_t frame0, int64_t T, double* spec, double* mag);
+int fluhip_debug_stft_frames_f64(fluhip_ctx* ctx, const double* padded, int64_t B, int64_t n, int64_t guard, int64_t win,
+                                 int64_t fft, int64_t hop, int64_t frame0, int64_t T, double* spec, double* mag);
 
 /* ---- algorithm::NMF ------------------------------------------------------------------- */
 /* Replaces NMF::process(X, W1, H1, V1, rank, nIterations, updateW, updateH, randomSeed, W0, H0)

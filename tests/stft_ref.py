@@ -352,6 +352,56 @@ NO_BLOCK_CORPORA = [(2, n_for(9, 128), 512, 512, 128), (2, n_for(9, 256), 1023, 
 BUFSTFT_SHAPES = [(n_for(21, 256), 1024, 1024, 256), (n_for(21, 128), 400, 512, 128)]      # one block shape, one generic shape
 
 
+# frames OUTSIDE their buffer (fluhip_debug_stft_frames_*): (win, fft, float types) of every kernel form -- the block form at
+# its three sizes with a full and a short even window, a generic power of two, a generic odd window with no block form, the
+# largest on-chip size, and the global-memory passes (float32 only)
+OUTSIDE_CASES = ([(w, f, ("float32", "float64")) for f in BLOCK_FFTS for w in (f, SHORT_EVEN_WINDOWS[f])]
+                 + [(64, 64, ("float32", "float64")), (1023, 1024, ("float32", "float64")), (8192, 8192, ("float32", "float64")),
+                    (16384, 16384, ("float32",))])
+OUTSIDE_B = 3
+OUTSIDE_GUARD_VALUE = 1e30
+SILENT_BIN = 2.0 ** -511           # sqrt(DBL_MIN): the block kernel's OWN magnitude of an exactly silent bin (fft_core.h mag_sumsq)
+
+
+def outside_geometry(fft, odd_hop, shift):
+    """(n, hop, frame0, T, guard) of a run of frames from more than two transforms before the buffer to at least one behind it:
+    n = fft + fft / 2 + 5, hop = fft / 4 (or one less: odd bases), frame0 = -(2 fft + hop) + shift, the last frame at or behind
+    n + fft; guard as far as the furthest frame (padded to the transform) lies outside, plus fft"""
+    n, hop = fft + fft // 2 + 5, fft // 4 - int(odd_hop)
+    frame0 = -(2 * fft + hop) + shift
+    T = -(-(n + fft - frame0) // hop) + 1
+    assert frame0 + (T - 1) * hop >= n + fft > frame0 + (T - 2) * hop
+    guard = max(-frame0, frame0 + (T - 1) * hop + fft - n) + fft
+    return n, hop, frame0, T, guard
+
+
+def outside_shifts(fft, odd_hop):
+    """-1, 0, +1, and the shifts that put a frame at s0 = -fft (no sample of the buffer) and -fft + 1 (one sample, with
+    win = fft) at the front -- 0 and +1 themselves at hop = fft / 4 -- and at n - 1 (one sample) and n (none) at the back"""
+    n, hop, frame0, _, _ = outside_geometry(fft, odd_hop, 0)
+    front, back = (-fft - frame0) % hop, (n - frame0) % hop
+    return sorted({-1, 0, 1, front, front + 1, back - 1, back})
+
+
+def outside_starts(fft, odd_hop):
+    """every frame start the shifts of a case produce"""
+    out = set()
+    for sh in outside_shifts(fft, odd_hop):
+        _, hop, frame0, T, _ = outside_geometry(fft, odd_hop, sh)
+        out |= {frame0 + t * hop for t in range(T)}
+    return out
+
+
+def outside_input(n, guard, seed, dtype):
+    """[OUTSIDE_B, guard + n + guard]: each buffer's samples (seeds seed, seed + 1, ...: a neighbour's samples are the nearest
+    wrong answer) between guards of 1e30; and the list of the buffers on their own"""
+    bufs = [dynamics(n, seed + b, dtype) for b in range(OUTSIDE_B)]
+    padded = np.full((OUTSIDE_B, n + 2 * guard), OUTSIDE_GUARD_VALUE, dtype=dtype)
+    for b, x in enumerate(bufs):
+        padded[b, guard:guard + n] = x
+    return padded, bufs
+
+
 def round_blocks(deal):
     """the blocks dealt to the first and the last workgroup of rounds one and two: [(buffer, first frame)]"""
     out = []

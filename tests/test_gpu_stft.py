@@ -21,6 +21,10 @@ Measured on an MI355X (the worst frame of each class; its bar in brackets):
                 ragged   4.1e-16 / 4.5e-16 / 4.4e-16      no block form: fft 512 4.1e-16, 1023 / 1024 4.4e-16, 8192 4.5e-16, 16384 6.1e-16
   magnitudes from hypot of the own spectrum   2.1e-16 at worst (4.4e-16)      BufSTFT, float32   4.3e-8 .. 5.7e-8 (6.0e-8)
   every bin-major copy bit-identical to the transpose and zero in its padding.  No form of K1 missed its bar.
+  frames outside their buffer (fluhip_debug_stft_frames_*, every form, float and double input, guards of 1e30 around each buffer):
+                fft 64  5.7e-16 (4.5e-15)    block 1024 / 2048 / 4096   8.0e-16 / 7.1e-16 / 9.3e-16 (6.3e-15 / 5.7e-15 / 7.2e-15)
+                fft 8192   1.1e-15 (7.6e-15)    big passes 16384   1.3e-15 (8.0e-15)    every frame with no sample of its buffer
+                exactly zero, the kernels' own magnitudes of such a frame 0 or 2^-511; no guard value in any result.
 
 Which deliberate breaks only this measure sees is shown on the CPU (test_stft_ref.py): one pass's twiddles at float32 in the
 quiet frames reads 7e-14 on the old measure (max |a - b| / max |b| < 1e-12 over the spectrogram) and 2.5e-8 here; stale
@@ -250,3 +254,56 @@ def test_bufstft_forward_padding_modes(ctx, n, win, fft, hop, mode):
     assert mag32.shape == (fft // 2 + 1, T)
     ref = R.stft_ld(x, win, fft, hop, offset=off, T=T)
     hold(f"BufSTFT mode {mode} win {win} fft {fft}", (None, mag32.T.astype(np.float64)), ref, FLOAT32_ULP + STFT_BAR[fft])
+
+
+# ---- frames outside their buffer, every kernel form ---------------------------------------------------------------------------
+@pytest.mark.parametrize("odd_hop", [False, True], ids=["hop_quarter", "odd_hop"])
+@pytest.mark.parametrize("win,fft,dtypes", R.OUTSIDE_CASES, ids=lambda v: str(v) if isinstance(v, int) else "")
+def test_frames_outside_the_buffer(ctx, win, fft, dtypes, odd_hop):
+    """fluhip_debug_stft_frames_*: frames from more than two transforms before their buffer to at least one behind it, which
+    STFT::process' framing never produces and the control clients' latency does; three buffers side by side, each between guards
+    of 1e30 that reach past every frame.  Every frame of every buffer against the long double restatement at STFT_BAR[fft]; a frame
+    with no sample of its buffer exactly zero (frame_err); no guard value, no neighbour's sample in any result.
+    A second launch without the spectrum (the kernels' SPEC = false forms) returns the kernels' OWN magnitudes, as the corpus and
+    the control clients consume them: the same bar on every frame with a sample of its buffer, and every bin of the others 0 or
+    R.SILENT_BIN (the block form's sum of squares starts from DBL_MIN, fft_core.h mag_sumsq: sqrt(DBL_MIN) = 2^-511 exactly)."""
+    form = {True: "big", False: "block" if win % 2 == 0 and fft in R.BLOCK_FFTS else "generic"}[fft > 8192]
+    for dtype in dtypes:
+        for shift in R.outside_shifts(fft, odd_hop):
+            n, hop, frame0, T, guard = R.outside_geometry(fft, odd_hop, shift)
+            assert R.dispatch(win, fft, R.OUTSIDE_B, T, False, dtype == "float32", n, hop)["branch"] == form
+            padded, bufs = R.outside_input(n, guard, 120, dtype)
+            spec, mag = ctx.debug_stft_frames(padded, n, guard, win, fft, hop, frame0, T)
+            _, own = ctx.debug_stft_frames(padded, n, guard, win, fft, hop, frame0, T, want_spec=False)
+            assert spec.shape == mag.shape == own.shape == (R.OUTSIDE_B, T, fft // 2 + 1)
+            # (|x| < 2: a guard sample would read 1e30 x the window)
+            assert np.abs(spec).max() < fft and mag.max() < fft and own.max() < fft
+            silent = 0
+            for b, x in enumerate(bufs):
+                what = f"outside {dtype} win {win} fft {fft} hop {hop} frame0 {frame0} buffer {b}"
+                ref = R.stft_ld(x, win, fft, hop, offset=frame0, T=T)
+                hold(what, (spec[b], mag[b]), ref, STFT_BAR[fft])
+                live = np.abs(ref[1]).max(axis=1) != 0
+                hold(what + " own magnitudes", (None, own[b][live]), (None, ref[1][live]), STFT_BAR[fft])
+                assert np.isin(own[b][~live], (0.0, R.SILENT_BIN)).all(), what
+                silent += int((~live).sum())
+            assert silent >= 2 * R.OUTSIDE_B                             # frames with no sample of their buffer, front and back
+
+
+def test_frames_outside_an_empty_buffer(ctx):
+    """n = 0: every frame of every form exactly zero, whatever lies around the (empty) buffer"""
+    for win, fft, dtypes in R.OUTSIDE_CASES:
+        for dtype in dtypes:
+            guard, hop, T = 4 * fft, fft // 4, 9
+            padded = np.full((2, 2 * guard), R.OUTSIDE_GUARD_VALUE, dtype=dtype)
+            spec, mag = ctx.debug_stft_frames(padded, 0, guard, win, fft, hop, -fft - hop, T)
+            _, own = ctx.debug_stft_frames(padded, 0, guard, win, fft, hop, -fft - hop, T, want_spec=False)
+            assert not spec.any() and not mag.any() and np.isin(own, (0.0, R.SILENT_BIN)).all(), (win, fft, dtype)
+
+
+def test_frames_outside_the_buffer_refuses_short_guards(ctx):
+    import fluhip
+    n, hop, frame0, T, guard = R.outside_geometry(1024, False, 0)
+    padded, _ = R.outside_input(n, guard - 1, 120, "float32")
+    with pytest.raises(fluhip.FluhipError, match="guards must reach"):
+        ctx.debug_stft_frames(padded, n, guard - 1, 1024, 1024, hop, frame0, T)

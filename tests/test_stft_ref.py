@@ -363,3 +363,30 @@ def test_the_shapes_reach_every_branch():
     # shapes without a block form
     assert [R.dispatch(w, f, B, R.num_frames(n, h), True)["branch"] for B, n, w, f, h in R.NO_BLOCK_CORPORA] == ["generic"] * 3 + ["big"]
     assert [R.dispatch(w, f, 1, 21)["branch"] for _, w, f, _ in R.BUFSTFT_SHAPES] == ["block", "generic"]
+
+
+def test_the_frames_outside_the_buffer_reach_every_form_and_every_edge():
+    """the shape table of test_gpu_stft.py's frames outside their buffer: every kernel form is met, the frames run from more than
+    two transforms before the buffer to at least one behind it, and the shifts put a frame on each edge -- s0 = -fft (no sample of
+    the buffer) and -fft + 1 (one) in front, n - 1 (one) and n (none) behind -- with the guards reaching past every frame"""
+    forms = {}
+    for win, fft, dtypes in R.OUTSIDE_CASES:
+        for odd_hop in (False, True):
+            n, hop, frame0, T, guard = R.outside_geometry(fft, odd_hop, 0)
+            assert n == fft + fft // 2 + 5 and hop == fft // 4 - odd_hop and frame0 == -(2 * fft + hop) and 20 <= T <= 26
+            d = R.dispatch(win, fft, R.OUTSIDE_B, T, False, True, n, hop)
+            forms.setdefault(d["branch"], set()).add((win, fft))
+            starts = R.outside_starts(fft, odd_hop)
+            assert {-fft, -fft + 1, n - 1, n} <= starts, (win, fft, odd_hop)
+            assert min(starts) < -2 * fft and max(starts) >= n + fft
+            assert {-1, 0, 1} <= set(R.outside_shifts(fft, odd_hop)) and len(R.outside_shifts(fft, odd_hop)) <= 7
+            for sh in R.outside_shifts(fft, odd_hop):
+                n, hop, frame0, T, guard = R.outside_geometry(fft, odd_hop, sh)
+                assert guard >= -frame0 + fft and guard >= frame0 + (T - 1) * hop + fft - n + fft
+            # frames wholly inside, on even and odd bases: the float gather's aligned and clamped interior paths both
+            inside = [s for s in starts if 0 <= s and s + fft <= n]
+            assert {s % 2 for s in inside} == {0, 1}
+        assert dtypes == (("float32",) if fft > 8192 else ("float32", "float64"))
+    assert forms["block"] == {(f, f) for f in R.BLOCK_FFTS} | {(R.SHORT_EVEN_WINDOWS[f], f) for f in R.BLOCK_FFTS}
+    assert forms["generic"] == {(64, 64), (1023, 1024), (8192, 8192)} and forms["big"] == {(16384, 16384)}
+    assert all(f in STFT_BAR for _, f, _ in R.OUTSIDE_CASES)
